@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of Prismer-BASE caption fine-tuning (224^2, 6 experts, batch 32 / GPU, freeze_vision,
 T = 30, bf16 storage / fp32 accumulate) on N MI355X -- BASELINE.json `metric`, config[2] (N=1) / config[3] (N=8).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = the full training iteration of the reference loop (train_caption.py:126-135): LR schedule, zero_grad, forward
@@ -10,7 +10,10 @@ One step = the full training iteration of the reference loop (train_caption.py:1
 label-smoothed CE), backward, gradient all-reduce over RCCL (N > 1) and fused AdamW over the 242.4 M trainable parameters.
 Synthetic inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra legs (rank 0, N = 1 only):
+--dump-outputs DIR (rank 0): after the timed steps, what the last one computed is written as float32 .npy files (dump_outputs).
+Weights, inputs and the instance-embedding draws are seeded, so two runs with the same arguments see identical inputs.
+
+Extra legs (rank 0, N = 1 only, with --full; a plain run times the headline steps and nothing else):
   roofline      the bf16 MFMA GEMM kernel family: algorithmic FLOPs (2*M*N*K per launch) / summed launch durations, measured
                 with HIP events on the launch stream in an instrumented (eager, non-graph) pass of the same step
   cpu_baseline  the CPU oracle (oracle/prismer_oracle.py, fp32) on a bounded sample of the same workload: batch 8, every logical CPU of
@@ -23,6 +26,7 @@ import ctypes
 import json
 import math
 import os
+import random
 import sys
 import time
 
@@ -85,6 +89,7 @@ def build_trainer(batch, use_graph, rank, T=30, workload='base_caption', freeze=
     from prismer_amd.model.prismer_vqa import PrismerVQA
     from prismer_amd.trainer import Trainer
     torch.manual_seed(0)                                   # identical random-init weights on every rank
+    random.seed(0)                                         # instance-embedding draws (Trainer._host_prologue): identical from run to run
     if workload == 'large_vqa':                            # BASELINE config 5: Prismer-LARGE VQA, 480^2, T = 35 + 5
         dims = pcfg.prismer_large()
         cfg = {'experts': pcfg.CAPTION_EXPERTS, 'image_resolution': 480, 'prismer_model': 'prismer_large', 'freeze': 'freeze_vision'}
@@ -351,6 +356,27 @@ def _leaves(t):
         yield t
 
 
+DUMP_SAMPLE = 1 << 21           # parameters kept per store: 2 x 8 MB of float32, a fixed seeded sample of the 242.4 M updated weights
+
+
+def dump_outputs(tr, loss, out_dir):
+    """What a caller of Trainer.step() receives from the last timed step, as float32 .npy files in out_dir: the returned loss and a fixed
+    sample (seeded indices, sorted) of every store's trainable fp32 master weights after the step's AdamW update.  (BatchNorm running
+    statistics are left out: they average every step since start-up, warm-up included, rather than being what the last step computed.)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {'loss': loss.detach().float().reshape(-1)}
+    for name, st in zip(('encoder', 'decoder'), tr.stores):
+        w = st.master[:st.n_train]
+        if st.n_train > DUMP_SAMPLE:
+            idx = torch.randint(0, st.n_train, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            w = w[idx.to(w.device)]
+        arrays[f'{name}_weights_sample'] = w.float()
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -373,11 +399,18 @@ def main():
     ap.add_argument('--shard', default='none', choices=['none', 'zero1', 'rs_ag'],
                     help='N > 1: none = replicated AdamW behind an all-reduce; zero1 = sharded AdamW + broadcasts; rs_ag = reduce-scatter + '
                          'sharded AdamW + all-gather (FSDP SHARD_GRAD_OP pattern)')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the secondary workloads (BASELINE configs 2 and 5) of the N=1 line')
+    ap.add_argument('--full', action='store_true',
+                    help='N=1: also run the extra legs after the headline (roofline, cpu_baseline, secondary); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32, rank 0)')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the secondary workloads (BASELINE configs 2 and 5) of the N=1 line')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the cpu_baseline leg')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline leg')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_roofline = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, rendezvous on
@@ -460,6 +493,8 @@ def main():
         check_loss('headline', first_loss, final_loss)       # raises: no line is printed for a step that did not compute a sane loss
     if not args.no_graph and not (tr.use_graph and tr.graphs is not None):
         raise SystemExit('bench.py: hipGraph replay was requested but the Trainer is running eager launches')
+    if args.dump_outputs and rank == 0:                    # before the --full legs: the roofline pass runs more steps on this Trainer
+        dump_outputs(tr, loss, args.dump_outputs)
 
     out = {
         'metric': {'base_caption': 'images/sec Prismer-BASE caption train, 224^2 + 6 experts, bs32/GPU',

@@ -1,14 +1,80 @@
 """Golden-case definitions shared by make_golden.py (runs the REFERENCE, build container only) and the tests
 (which regenerate the identical weights / inputs from prismer_amd.synth and compare against the stored
 reference outputs)."""
+import io
+import os
 import random
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from prismer_amd import config, synth
 
 INSTANCE_SEED = 7     # random.seed before every encoder call: vit.py:145-147 draws from Python's `random`
+
+GOLD = os.path.dirname(os.path.abspath(__file__))
+PART_BYTES = 960 * 1024      # every committed file stays below 1 MiB: a fixture is stored as <name>.npz or as parts <name>.<i>.npz
+
+
+def _zsize(arrays):
+    b = io.BytesIO()
+    np.savez_compressed(b, **arrays)
+    return b.tell()
+
+
+def save(name, arrays):
+    """Writes the fixture `name` as compressed parts below PART_BYTES each: one <name>.npz when it fits, otherwise <name>.0.npz,
+    <name>.1.npz, ...; an array too large for one part is cut along axis 0 into entries '<key>@<j>'.  load() reassembles it exactly."""
+    for p in [os.path.join(GOLD, name + '.npz')] + [os.path.join(GOLD, f'{name}.{i}.npz') for i in range(1000)]:
+        if os.path.isfile(p):
+            os.remove(p)
+    items = []                                             # (key, array, compressed size on its own)
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        z = _zsize({k: v})
+        n = -(-z // (PART_BYTES // 2))
+        if n == 1:
+            items.append((k, v, z))
+        else:
+            assert v.ndim >= 1 and v.shape[0] >= n, (name, k, v.shape)
+            items += [(f'{k}@{j}', c, _zsize({k: c})) for j, c in enumerate(np.array_split(v, n))]
+    parts, cur, used = [], {}, 0
+    for k, v, z in items:
+        if cur and used + z > PART_BYTES:
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = v
+        used += z
+    parts.append(cur)
+    paths = [os.path.join(GOLD, name + '.npz')] if len(parts) == 1 else [os.path.join(GOLD, f'{name}.{i}.npz') for i in range(len(parts))]
+    for p, part in zip(paths, parts):
+        np.savez_compressed(p, **part)
+        assert os.path.getsize(p) < 1 << 20, p
+    return paths
+
+
+def load(name):
+    """{key: array} of the fixture `name` (see save())."""
+    p = os.path.join(GOLD, name + '.npz')
+    paths = [p] if os.path.isfile(p) else []
+    while not os.path.isfile(p) and os.path.isfile(os.path.join(GOLD, f'{name}.{len(paths)}.npz')):
+        paths.append(os.path.join(GOLD, f'{name}.{len(paths)}.npz'))
+    if not paths:
+        raise FileNotFoundError(f'no fixture {name} under {GOLD}')
+    out, chunks = {}, {}
+    for path in paths:
+        with np.load(path) as z:
+            for k in z.files:
+                base, sep, j = k.rpartition('@')
+                if sep:
+                    chunks.setdefault(base, []).append((int(j), z[k]))
+                    out.setdefault(base, None)
+                else:
+                    out[k] = z[k]
+    for k, cs in chunks.items():
+        out[k] = np.concatenate([c for _, c in sorted(cs, key=lambda t: t[0])])
+    return out
 
 
 def _dims(name):

@@ -98,9 +98,8 @@ def run_case(name):
         out['ac_norm.' + n] = np.float64(abs(p.grad.double().norm().item() - float(out['gnorm.' + n])) / (float(out['gnorm.' + n]) + 1e-30))
         # FULL-tensor error of autocast (exact, the reference gradient is still at hand): yardstick of the projection test
         out['ac_rel.' + n] = np.float64((p.grad.double() - ref_full[n].double()).norm().item() / (float(out['gnorm.' + n]) + 1e-30))
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), name + '.npz')
-    np.savez_compressed(path, **out)
-    print(f'{name}: wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB)  loss_eval={out["loss_eval"]}  '
+    paths = C.save(name, out)
+    print(f'{name}: wrote {paths} ({sum(os.path.getsize(p) for p in paths) / 1e6:.2f} MB)  loss_eval={out["loss_eval"]}  '
           f'total_train={out["total_train"]}  trainable={len(names)}')
 
 
@@ -173,9 +172,8 @@ def run_drop_case(name):
             out[pre + 'ac_samp.' + n] = np.float64(np.linalg.norm(sm - ref_s) / (np.linalg.norm(ref_s) + 1e-30))
             out[pre + 'ac_norm.' + n] = np.float64(abs(p.grad.double().norm().item() - gn) / (gn + 1e-30))
             out[pre + 'ac_rel.' + n] = np.float64((p.grad.double() - ref_full[si][n].double()).norm().item() / (gn + 1e-30))
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), name + '_drop.npz')
-    np.savez_compressed(path, **out)
-    print(f'{name}_drop: wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB)  total_train s1={out["s1.total_train"]} s2={out["s2.total_train"]}')
+    paths = C.save(name + '_drop', out)
+    print(f'{name}_drop: wrote {paths} ({sum(os.path.getsize(p) for p in paths) / 1e6:.2f} MB)  total_train s1={out["s1.total_train"]} s2={out["s2.total_train"]}')
 
 
 def run_traj_case(name):
@@ -240,9 +238,8 @@ def run_traj_case(name):
     out['ac_losses'] = np.array(ac_losses, dtype=np.float64)
     for n, dl in ac_delta.items():
         out['ac_drel.' + n] = np.float64((dl.double() - delta[n].double()).norm().item() / (float(out['dnorm.' + n]) + 1e-30))
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), name + '_traj.npz')
-    np.savez_compressed(path, **out)
-    print(f'{name}_traj: wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB)  losses={losses}  autocast losses={ac_losses}')
+    paths = C.save(name + '_traj', out)
+    print(f'{name}_traj: wrote {paths} ({sum(os.path.getsize(p) for p in paths) / 1e6:.2f} MB)  losses={losses}  autocast losses={ac_losses}')
 
 
 if __name__ == '__main__':

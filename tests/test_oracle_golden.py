@@ -1,7 +1,6 @@
 """CPU: the oracle restatement (oracle/prismer_oracle.py) against the committed reference outputs
 (tests/golden/*.npz, minted by tests/golden/make_golden.py from the reference module classes), and
 against the live reference when /root/reference is mounted."""
-import os
 import random
 
 import numpy as np
@@ -12,12 +11,11 @@ from oracle import prismer_oracle as O
 from oracle import ref_harness as RH
 from tests.golden import cases as C
 
-GOLD = os.path.join(os.path.dirname(__file__), 'golden')
 TOL = 2e-5          # fp32 vs fp32, different op order (packed MHA vs explicit matmul)
 
 
 def load(name):
-    return np.load(os.path.join(GOLD, name + '.npz'))
+    return C.load(name)
 
 
 def rel(a, b):

@@ -3,7 +3,6 @@
   (2) the CPU oracle (oracle/prismer_oracle.py) on the same synthetic weights/inputs.
 Tolerances follow SURVEY 8c (bf16 storage / fp32 accumulate vs an fp32 reference):
   encoder output, logits  rel-Frobenius <= 2e-2 ; per-sample loss rel <= 2e-3 ; gradients rel-Frobenius <= 6e-2."""
-import os
 import random
 
 import numpy as np
@@ -19,7 +18,6 @@ from tests.golden import cases as C
 from tests.util import rel_fro
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), 'golden')
 TOL_ACT, TOL_LOSS, TOL_GRAD = 2e-2, 2e-3, 5e-2      # (gradient bar 5e-2 since round 6: SURVEY 8c; 6e-2 before)
 TOL_GRAD_SAMPLED = 6e-2      # the 16-ENTRY sample is a noisy estimator of a tensor's error (B = 1 fixtures sit at 0.84 of 2 x this): it keeps the round-2 bar;
                              # the full-tensor checks (norm, 16 projections, gfull) carry the tightened one
@@ -61,7 +59,7 @@ def run(enc, dec, case, x, ids, mask, labels, weights):
 
 @pytest.mark.parametrize('name', list(C.CASES))
 def test_eval_matches_reference_golden(name):
-    g = np.load(os.path.join(GOLD, name + '.npz'))
+    g = C.load(name)
     case = C.Case(name)
     enc, dec, _, _ = build(case)
     enc.eval(); dec.eval()
@@ -78,7 +76,7 @@ def test_eval_matches_reference_golden(name):
 
 @pytest.mark.parametrize('name', ['tiny_caption', 'tiny_vqa', 'tiny_bicubic', 'tiny_z', 'tiny_vqa_head', 'base_caption', 'base_b8'])
 def test_train_mode_and_gradients_match_reference_golden(name):
-    g = np.load(os.path.join(GOLD, name + '.npz'))
+    g = C.load(name)
     case = C.Case(name)
     enc, dec, _, _ = build(case)
     set_freeze(enc, dec)
@@ -183,7 +181,7 @@ def test_trainer_step_matches_oracle_adamw():
         # capture warm-up is side-effect free (round 2): the first replayed step is the first step, like the eager one
         assert math_close(loss, ls.mean().item(), 2e-3), (use_graph, loss, ls.mean().item())
     loss, sd = results[0]
-    g = np.load(os.path.join(GOLD, 'tiny_caption.npz'))
+    g = C.load('tiny_caption')
     # (1) gradients left in the flat fp32 buffers by the hand-scheduled backward == oracle autograd gradients
     errs = []
     for n, v in leaves.items():
@@ -511,7 +509,7 @@ def _hipgraph_step_vs_golden(name, force_big=False):
     from prismer_amd.trainer import cosine_lr
     import ctypes
     from prismer_amd import _lib
-    g = np.load(os.path.join(GOLD, name + '.npz'))
+    g = C.load(name)
     case = C.Case(name)
     lr = 1e-4
     counts = (ctypes.c_int64 * 16)()
@@ -585,7 +583,7 @@ def test_trainer_hipgraph_dropout_steps_match_reference_golden(name):
     seed is advanced by a kernel inside the graph: fresh masks per replay).  Same bars as the dropout-free test.  Pins the Philox-7
     generator, the embedding / GEMM-epilogue / LayerNorm-backward mask regeneration and the quad-cooperative dK/dV dropout words end to end."""
     from tests.util import splitmix64
-    g = np.load(os.path.join(GOLD, name + '_drop.npz'))
+    g = C.load(name + '_drop')
     case = C.Case(name)
     tr, m = _pinned_trainer(case, use_graph=True, lr=0.0, p_drop=0.1)
     assert case.dims.hidden_dropout_prob == case.dims.attention_probs_dropout_prob == 0.1
@@ -601,7 +599,7 @@ def test_trainer_hipgraph_dropout_steps_match_reference_golden(name):
         want = float(g[f's{si}.total_train'])
         print(name, 'step', si, 'loss', loss.item(), 'reference under the same masks', want)
         assert math_close(loss.item(), want, TOL_LOSS), (si, loss.item(), want)
-        gv = {k[3:]: g[k] for k in g.files if k.startswith(f's{si}.')}
+        gv = {k[3:]: g[k] for k in g if k.startswith(f's{si}.')}
         gv['requires_grad'] = g['requires_grad']
         named = {}
         for pref, st in (('expert_encoder.', tr.stores[0]), ('text_decoder.', tr.stores[1])):
@@ -624,7 +622,7 @@ def test_trainer_hipgraph_trajectory_matches_reference_loop(name):
     (16 fixed projections: a full-tensor estimate) and the BatchNorm running statistics after four updates.  AdamW's first steps move every entry
     by ~lr whatever the gradient's size, so entries whose gradient is round-off flip sign under ANY bf16 arithmetic: the yardstick's own
     displacement error is 8 % in the median; the bar is 2x the yardstick per tensor (floor 15 %), the loss curve is held to 2e-3."""
-    g = np.load(os.path.join(GOLD, name + '_traj.npz'))
+    g = C.load(name + '_traj')
     case = C.Case(name)
     assert (C.TRAJ_LR, C.TRAJ_MIN_LR, C.TRAJ_WD, C.TRAJ_TOTAL) == (5e-5, 0.0, 0.05, 10)         # what _pinned_trainer builds (configs/caption.yaml:12-14)
     tr, m = _pinned_trainer(case, use_graph=True, lr=C.TRAJ_LR, p_drop=0.1, keep_grads=False)
@@ -941,7 +939,7 @@ def test_caption_head_train_forward_matches_reference_golden(name):
     """PrismerCaption.forward(train=True) (prismer_caption.py:17-34): the head builds the labels itself (pads and the prompt ->
     -100) and returns loss.mean(); compared with the reference's total on the same ids."""
     from prismer_amd.model.prismer_caption import PrismerCaption
-    g = np.load(os.path.join(GOLD, name + '.npz'))
+    g = C.load(name)
     case = C.Case(name)
     cap = _head(PrismerCaption, case)
     x, ids, mask, labels, _ = case.inputs()
@@ -957,7 +955,7 @@ def test_vqa_head_train_forward_matches_reference_golden():
     """PrismerVQA.forward(train=True) (prismer_vqa.py:18-42): question ‖ answer concatenation with pads in the middle of a row,
     answer-span targets, (weights * loss).mean()."""
     from prismer_amd.model.prismer_vqa import PrismerVQA
-    g = np.load(os.path.join(GOLD, 'tiny_vqa_head.npz'))
+    g = C.load('tiny_vqa_head')
     case = C.Case('tiny_vqa_head')
     vqa = _head(PrismerVQA, case)
     x = case.inputs()[0]
@@ -1065,7 +1063,7 @@ def test_trainer_pretrain_recipe_freeze_lang_vision_and_warmup():
     ls.mean().backward()
     assert math_close(loss.item(), ls.mean().item(), TOL_LOSS)
     assert sorted(grads) == sorted(leaves)
-    g = np.load(os.path.join(GOLD, 'tiny_caption.npz'))               # autocast yardstick of the same modules (freeze_vision fixture)
+    g = C.load('tiny_caption')               # autocast yardstick of the same modules (freeze_vision fixture)
     bad = []
     for n, v in leaves.items():
         ref = v.grad

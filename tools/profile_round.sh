@@ -1,11 +1,11 @@
 #!/bin/bash
-# Profile set of a round (the recipe behind profiles/rN_*): default bench line, rocprofv3 kernel trace of the bench under graph replay, three
+# Profile set of a round (the recipe behind profiles/rN_*): full bench line (--full), rocprofv3 kernel trace of the bench under graph replay, three
 # PMC passes (eager; FETCH_SIZE, WRITE_SIZE, MFMA busy -- separate runs, kernel-trace only: the pool refuses PMC + other trace domains),
 # per-kernel tables, phase times, secondary workload traces, two-rank dry run on one GPU.      bash tools/profile_round.sh r5 [outdir]
 p=${1:-r5}; out=${2:-gpurun_out/${p}_prof}; mkdir -p $out
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd /root/repo
 export TMPDIR=/tmp
-timeout 600 python bench.py --steps 20 --warmup 5 > $out/${p}_bench_n1.json 2> $out/bench_n1.err; tail -c 300 $out/${p}_bench_n1.json; echo
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $out/${p}_bench_n1.json 2> $out/bench_n1.err; tail -c 300 $out/${p}_bench_n1.json; echo
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/kt -o kt -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-secondary > $out/kt.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 900 rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o pmc -- python bench.py --steps 2 --warmup 1 --no-graph --no-cpu-baseline --no-roofline --no-secondary > $out/pmc_$c.log 2>&1
