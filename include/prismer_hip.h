@@ -208,6 +208,26 @@ int ph_attention_bwd(const ph_attn_bwd_args* args, hipStream_t stream);
  * registers.  small_query_kernels = 0 forces the streaming kernels for every launch (A/B, tests), 1 restores the default, 2 = default without
  * the head-resident kernels, < 0 only queries.  Returns the previous setting. */
 int ph_attention_tuning(int small_query_kernels);
+/* Shared-prefix attention, forward only (rank inference: model/prismer_caption.py:59-112, model/prismer_vqa.py:64-113).  Row r of
+ * R continuation rows (queries and keys t = 0 .. Tc-1) attends to two key segments:
+ *   prefix keys 0 .. Tp-1 of prefix row r / group  (key_mask prefix_mask[(r/group)*pm_bs + j], no causal cut: the whole prefix
+ *                                                  precedes every continuation token),
+ *   its own continuation keys 0 .. Tc-1             (key_mask cont_mask[r*cm_bs + j], causal: key j > query i is cut).
+ * That is ph_attention_fwd on the concatenated sequence [prefix, continuation] with causal = 1 and the concatenated key mask, for
+ * query positions Tp .. Tp+Tc-1: masked and causal-cut keys score finfo.min, keys beyond a segment do not exist.  One prefix row's
+ * K / V serves `group` continuation rows without being copied.  Tensor layout as ph_attn_fwd_args: token (b, t), head h, channel c
+ * of q lives at q + b*q_bs + t*q_ts + h*dh + c (b = r for q / ck / cv / o, b = r / group for pk / pv).  Null masks = every key live.
+ * Limits: dh = 64, 1 <= Tc <= 32, 0 <= Tp <= 288 (pk / pv may be null when Tp = 0), group >= 1, R % group == 0; anything else
+ * is rejected with PH_ERR_BAD_ARG before any launch.  No lse, no dropout, no backward. */
+typedef struct {
+  const void* q; const void* pk; const void* pv; const void* ck; const void* cv; void* o;
+  int64_t q_bs, q_ts, pk_bs, pk_ts, pv_bs, pv_ts, ck_bs, ck_ts, cv_bs, cv_ts, o_bs, o_ts;
+  const uint8_t* prefix_mask; int64_t pm_bs;
+  const uint8_t* cont_mask; int64_t cm_bs;
+  int R, group, H, Tc, Tp, dh;
+  float scale;
+} ph_attn_prefix_fwd_args;
+int ph_attention_prefix_fwd(const ph_attn_prefix_fwd_args* args, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Encoder front end (vit.py:86-160).
@@ -305,6 +325,9 @@ typedef struct {
   void* out_f32;                  /* optional fp32 copy of `out` */
 } ph_embed_fwd_args;
 int ph_embed_fwd(const ph_embed_fwd_args* args, hipStream_t stream);
+/* ph_embed_fwd for a row that continues an earlier one (rank inference's continuation rows): real tokens take position
+ * pad + pos_base[b] + cumsum(ids != pad), pad tokens keep position pad.  pos_base: int32 [B], device memory. */
+int ph_embed_fwd_offset(const ph_embed_fwd_args* args, const int32_t* pos_base, hipStream_t stream);
 typedef struct {
   ph_embed_fwd_args f;
   const void* dout;               /* bf16 [B*T, H] */

@@ -111,6 +111,15 @@ class AttnBwdArgs(C.Structure):
                 ('dv_bs', c_i64), ('dv_ts', c_i64), ('delta', c_void_p)]
 
 
+class AttnPrefixFwdArgs(C.Structure):
+    _fields_ = [('q', c_void_p), ('pk', c_void_p), ('pv', c_void_p), ('ck', c_void_p), ('cv', c_void_p), ('o', c_void_p),
+                ('q_bs', c_i64), ('q_ts', c_i64), ('pk_bs', c_i64), ('pk_ts', c_i64), ('pv_bs', c_i64), ('pv_ts', c_i64),
+                ('ck_bs', c_i64), ('ck_ts', c_i64), ('cv_bs', c_i64), ('cv_ts', c_i64), ('o_bs', c_i64), ('o_ts', c_i64),
+                ('prefix_mask', c_void_p), ('pm_bs', c_i64), ('cont_mask', c_void_p), ('cm_bs', c_i64),
+                ('R', c_int), ('group', c_int), ('H', c_int), ('Tc', c_int), ('Tp', c_int), ('dh', c_int),
+                ('scale', c_float)]
+
+
 class EmbedFwdArgs(C.Structure):
     _fields_ = [('ids', c_void_p), ('B', c_int), ('T', c_int), ('H', c_int), ('pad_id', c_int),
                 ('word', c_void_p), ('pos', c_void_p), ('type', c_void_p),
@@ -132,6 +141,7 @@ _SIGS = {
     'ph_layernorm_bwd': (c_int, [C.POINTER(LayerNormBwdArgs), c_void_p]),
     'ph_attention_fwd': (c_int, [C.POINTER(AttnFwdArgs), c_void_p]),
     'ph_attention_bwd': (c_int, [C.POINTER(AttnBwdArgs), c_void_p]),
+    'ph_attention_prefix_fwd': (c_int, [C.POINTER(AttnPrefixFwdArgs), c_void_p]),
     'ph_patchify': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ph_resize_bilinear_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ph_gather_rows_bf16': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),
@@ -153,6 +163,7 @@ _SIGS = {
     'ph_gather_taps': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'ph_scatter_taps': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     'ph_embed_fwd': (c_int, [C.POINTER(EmbedFwdArgs), c_void_p]),
+    'ph_embed_fwd_offset': (c_int, [C.POINTER(EmbedFwdArgs), c_void_p, c_void_p]),
     'ph_embed_bwd': (c_int, [C.POINTER(EmbedBwdArgs), c_void_p]),
     'ph_softmax_gather_bf16': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'ph_ce_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

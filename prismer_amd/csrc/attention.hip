@@ -1416,6 +1416,195 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a)
   }
 }
 
+// Shared-prefix forward (rank inference, model/prismer_caption.py:59-112 and model/prismer_vqa.py:64-113 without the k-fold tiling): attn_fwd_small_kernel
+// with two key segments.  Block = (continuation row r, head h); unit u < np = ceil(Tp / 32) reads prefix keys u*32 .. of prefix row r / group (prefix
+// key mask, no causal cut), unit np reads the row's own Tc <= 32 continuation keys (continuation key mask, causal cut).  The V image in LDS is
+// [prefix units][continuation unit]; padding keys of a unit have key state -inf (they do not exist).  The `group` blocks of one prefix row re-read its
+// K / V from L2 / the Infinity Cache: nothing is copied per candidate.  QT = 2: all Tc <= 32 queries in every wave; no dropout, no lse.
+__global__ __launch_bounds__(256) void attn_prefix_fwd_kernel(ph_attn_prefix_fwd_args a) {
+  constexpr int DH = 64, QT = 2;
+  using C = Cfg<DH>;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int r = blockIdx.x / a.H, h = blockIdx.x % a.H;
+  const int pr = r / a.group;
+  const int np = (a.Tp + 31) >> 5, nunits = np + 1, rows_pad = nunits * 32;
+  bf16* vimg = reinterpret_cast<bf16*>(smem_raw);
+  float* kst = reinterpret_cast<float*>(vimg + rows_pad * C::RS);
+  float* obuf = reinterpret_cast<float*>(smem_raw);                         // merge images alias the V image (two barriers apart)
+  float* mbuf = obuf + 4 * QT * 16 * SM_OS;
+  float* lbuf = mbuf + 4 * QT * 16;
+  const bf16* Q = reinterpret_cast<const bf16*>(a.q) + r * a.q_bs + (int64_t)h * DH;
+  const bf16* PK = np ? reinterpret_cast<const bf16*>(a.pk) + pr * a.pk_bs + (int64_t)h * DH : nullptr;
+  const bf16* PV = np ? reinterpret_cast<const bf16*>(a.pv) + pr * a.pv_bs + (int64_t)h * DH : nullptr;
+  const bf16* CK = reinterpret_cast<const bf16*>(a.ck) + r * a.ck_bs + (int64_t)h * DH;
+  const bf16* CV = reinterpret_cast<const bf16*>(a.cv) + r * a.cv_bs + (int64_t)h * DH;
+  const uint8_t* pm = (np && a.prefix_mask) ? a.prefix_mask + pr * a.pm_bs : nullptr;
+  const uint8_t* cm = a.cont_mask ? a.cont_mask + r * a.cm_bs : nullptr;
+
+  int qi[QT];
+  bf16x8 qf[QT][C::KS];
+  f32x4 o[QT][C::DT];
+  float m[QT], lsum[QT];
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    qi[t] = t * 16 + c;
+    const int qr = qi[t] < a.Tc ? qi[t] : a.Tc - 1;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) qf[t][ks] = *reinterpret_cast<const bf16x8*>(Q + (int64_t)qr * a.q_ts + ks * 32 + g * 8);
+#pragma unroll
+    for (int d = 0; d < C::DT; ++d) o[t][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m[t] = NEG_MASK; lsum[t] = 0.f;
+  }
+  // K row fragments of this wave's units (rows beyond a segment re-read its last key; their key state is -inf)
+  bf16x8 kfu[SM_MAXU][2][C::KS];
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui) {
+    const int u = wave + 4 * ui;
+    if (u < nunits) {
+      const bool pre = u < np;
+      const bf16* Kb = pre ? PK : CK;
+      const int64_t ts = pre ? a.pk_ts : a.ck_ts;
+      const int n = pre ? a.Tp : a.Tc, k0 = pre ? u * 32 : 0;
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int kr = min(k0 + nt * 16 + c, n - 1);
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) kfu[ui][nt][ks] = *reinterpret_cast<const bf16x8*>(Kb + (int64_t)kr * ts + ks * 32 + g * 8);
+      }
+    }
+  }
+  if (np) sm_stage<SM_MAX_UNITS - 1>(vimg, PV, a.pv_ts, a.Tp, np * 32);
+  sm_stage<1>(vimg + np * 32 * C::RS, CV, a.cv_ts, a.Tc, 32);
+  for (int i = threadIdx.x; i < rows_pad; i += 256) {
+    const int j = i - np * 32;
+    kst[i] = j < 0 ? key_state(key_raw(pm, i, a.Tp), i, a.Tp) : key_state(key_raw(cm, j, a.Tc), j, a.Tc);
+  }
+#pragma unroll
+  for (int t = 0; t < QT; ++t)
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) settle(qf[t][ks]);
+  __syncthreads();
+
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui) {
+    const int u = wave + 4 * ui;
+    if (u >= nunits) break;
+    const int kbase = u * 32;
+    const bool cont = u == np;
+    f32x4 s[QT][2];
+    float mx[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) mx[t] = -INFINITY;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      f32x4 acc[QT];
+#pragma unroll
+      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < C::KS; ++ks)
+#pragma unroll
+        for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfu[ui][nt][ks], qf[t][ks], acc[t], 0, 0, 0);
+      const f32x4 st = *reinterpret_cast<const f32x4*>(kst + kbase + nt * 16 + g * 4);
+#pragma unroll
+      for (int t = 0; t < QT; ++t) {
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const int kj = nt * 16 + g * 4 + rr;                                 // key index inside the unit
+          acc[t][rr] = score_of(acc[t][rr], a.scale, st[rr], cont && kj > qi[t]);
+          mx[t] = fmaxf(mx[t], acc[t][rr]);
+        }
+        s[t][nt] = acc[t];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      const float m_new = fmaxf(m[t], xor_max(mx[t]));
+      const float alpha = __expf(m[t] - m_new);
+      float rs = 0.f;
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          const float p = __expf(s[t][nt][rr] - m_new);
+          rs += p;
+          s[t][nt][rr] = p;
+        }
+      rs = xor_sum(rs);
+      lsum[t] = lsum[t] * alpha + rs;
+      m[t] = m_new;
+#pragma unroll
+      for (int d = 0; d < C::DT; ++d) o[t][d] *= alpha;
+    }
+    bf16x8 pf[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) pf[t] = pack2(s[t][0], s[t][1]);
+#pragma unroll
+    for (int d = 0; d < C::DT; ++d) {
+      const bf16x8 vfr = frag_tr<DH>(vimg, kbase, d * 16, lane);
+#pragma unroll
+      for (int t = 0; t < QT; ++t) o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr, pf[t], o[t][d], 0, 0, 0);
+    }
+  }
+  // ---- no prefix (Tp = 0): wave 0 holds the whole result
+  if (nunits == 1) {
+    if (wave == 0) {
+#pragma unroll
+      for (int t = 0; t < QT; ++t)
+        if (qi[t] < a.Tc) {
+          const float inv = 1.0f / lsum[t];
+          bf16* O = reinterpret_cast<bf16*>(a.o) + r * a.o_bs + (int64_t)qi[t] * a.o_ts + (int64_t)h * DH;
+#pragma unroll
+          for (int d = 0; d < C::DT; ++d) {
+            const bf16x4 tt = {f2bf(o[t][d][0] * inv), f2bf(o[t][d][1] * inv), f2bf(o[t][d][2] * inv), f2bf(o[t][d][3] * inv)};
+            *reinterpret_cast<bf16x4*>(O + d * 16 + g * 4) = tt;
+          }
+        }
+    }
+    return;
+  }
+  // ---- merge the (max, sum, O^T) partials of the waves that held units (as attn_fwd_small_kernel)
+  __syncthreads();
+  if (wave < nunits) {
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      const int q = t * 16 + c;
+      if (g == 0) { mbuf[wave * QT * 16 + q] = m[t]; lbuf[wave * QT * 16 + q] = lsum[t]; }
+#pragma unroll
+      for (int d = 0; d < C::DT; ++d) *reinterpret_cast<f32x4*>(obuf + (wave * QT * 16 + q) * SM_OS + d * 16 + g * 4) = o[t][d];
+    }
+  }
+  __syncthreads();
+  const int q = threadIdx.x >> 2, col = (threadIdx.x & 3) * 16;
+  if (q < a.Tc) {
+    const int nw = nunits < 4 ? nunits : 4;
+    float M = NEG_MASK;
+    for (int w = 0; w < nw; ++w) M = fmaxf(M, mbuf[w * QT * 16 + q]);
+    float L = 0.f;
+    float acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+    for (int w = 0; w < nw; ++w) {
+      const float wgt = __expf(mbuf[w * QT * 16 + q] - M);
+      L += wgt * lbuf[w * QT * 16 + q];
+      const float* src = obuf + (w * QT * 16 + q) * SM_OS + col;
+#pragma unroll
+      for (int j4 = 0; j4 < 4; ++j4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + j4 * 4);
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) acc[j4 * 4 + rr] += wgt * v[rr];
+      }
+    }
+    const float inv = 1.0f / L;
+    bf16* O = reinterpret_cast<bf16*>(a.o) + r * a.o_bs + (int64_t)q * a.o_ts + (int64_t)h * DH + col;
+    bf16x8 o0, o1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { o0[j] = f2bf(acc[j] * inv); o1[j] = f2bf(acc[8 + j] * inv); }
+    *reinterpret_cast<bf16x8*>(O) = o0;
+    *reinterpret_cast<bf16x8*>(O + 8) = o1;
+  }
+}
 
 // Backward of a (batch, head) pair in ONE launch and ONE pass of the generator / exponentials (second version, round 5: the first one
 // recomputed scores and masks three times and fetched fragments from global memory inside the unit loop -- 36 us against 42 us of the two
@@ -1766,6 +1955,28 @@ extern "C" int ph_attention_fwd(const ph_attn_fwd_args* a, hipStream_t stream) {
 #undef PH_FWD_LAUNCH
 #undef PH_FWD
   PH_LAUNCH_CHECK("attn_fwd_kernel");
+  return PH_OK;
+}
+
+extern "C" int ph_attention_prefix_fwd(const ph_attn_prefix_fwd_args* a, hipStream_t stream) {
+  const char* who = "ph_attention_prefix_fwd";
+  PH_CHECK_ARG(a && a->q && a->ck && a->cv && a->o, "%s: null pointer", who);
+  PH_CHECK_ARG(a->dh == 64, "%s: head dim %d unsupported (64 only)", who, a->dh);
+  PH_CHECK_ARG(a->Tc >= 1 && a->Tc <= 32, "%s: Tc = %d continuation tokens outside 1..32", who, a->Tc);
+  PH_CHECK_ARG(a->Tp >= 0 && a->Tp <= 32 * (SM_MAX_UNITS - 1), "%s: Tp = %d prefix tokens outside 0..288", who, a->Tp);
+  PH_CHECK_ARG(a->Tp == 0 || (a->pk && a->pv), "%s: null prefix K / V with Tp = %d", who, a->Tp);
+  PH_CHECK_ARG(a->R > 0 && a->H > 0 && a->group >= 1 && a->R % a->group == 0, "%s: bad dims (R %d, group %d, H %d)", who, a->R, a->group, a->H);
+  PH_CHECK_ARG(((a->q_ts | a->pk_ts | a->pv_ts | a->ck_ts | a->cv_ts | a->o_ts | a->q_bs | a->pk_bs | a->pv_bs | a->ck_bs | a->cv_bs | a->o_bs) % 8) == 0,
+               "%s: strides must be multiples of 8 elements", who);
+  PH_CHECK_ARG((((uintptr_t)a->q | (uintptr_t)a->pk | (uintptr_t)a->pv | (uintptr_t)a->ck | (uintptr_t)a->cv | (uintptr_t)a->o) & 15) == 0,
+               "%s: pointers must be 16-B aligned", who);
+  PH_CHECK_ARG(((int64_t)a->Tp * a->pv_ts | (int64_t)a->Tc * a->cv_ts) < (1ll << 30),
+               "%s: a (row, head) slice must span < 2 GiB (V is staged through 32-bit buffer offsets)", who);
+  ProfScope prof__(PH_FAM_ATTN_FWD, 4.0 * a->R * (double)a->H * a->Tc * (double)(a->Tp + a->Tc) * a->dh, 0.0, stream);
+  const int rows_pad = (ceil_div(a->Tp, 32) + 1) * 32;
+  const int smem = set_smem(attn_prefix_fwd_kernel, sm_fwd_bytes(rows_pad, sm_merge_bytes<2>()));
+  hipLaunchKernelGGL(attn_prefix_fwd_kernel, dim3(a->R * a->H), dim3(256), smem, stream, *a);
+  PH_LAUNCH_CHECK("attn_prefix_fwd_kernel");
   return PH_OK;
 }
 

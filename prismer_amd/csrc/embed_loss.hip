@@ -21,7 +21,8 @@ __device__ __forceinline__ int position_id(const int64_t* ids_row, int t, int pa
   return ids_row[t] != pad ? cnt + pad : pad;
 }
 
-__global__ __launch_bounds__(256) void embed_fwd_kernel(ph_embed_fwd_args a) {
+// pos_base (ph_embed_fwd_offset, null for ph_embed_fwd): real tokens of row b continue an earlier row and take position pid + pos_base[b]
+__global__ __launch_bounds__(256) void embed_fwd_kernel(ph_embed_fwd_args a, const int32_t* pos_base) {
   int lane = threadIdx.x & 63;
   int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.B * a.T) return;
@@ -29,6 +30,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(ph_embed_fwd_args a) {
   const int64_t* ids_row = a.ids + (int64_t)b * a.T;
   int64_t id = ids_row[t];
   int pid = position_id(ids_row, t, a.pad_id, lane);
+  if (pos_base && id != a.pad_id) pid += pos_base[b];
   const int nch = a.H >> 2;
   const float* w = a.word + id * a.H;
   const float* p = a.pos + (int64_t)pid * a.H;
@@ -307,7 +309,17 @@ extern "C" int ph_embed_fwd(const ph_embed_fwd_args* a, hipStream_t stream) {
   ProfScope prof__(PH_FAM_EMBED_CE, 0.0, 0.0, stream);
   PH_CHECK_ARG(a->H % 4 == 0 && a->H <= MAX_CH * 256 && a->B > 0 && a->T > 0, "ph_embed_fwd: bad dims");
   PH_CHECK_ARG(!(a->drop_p > 0.f) || a->drop_seed, "ph_embed_fwd: dropout needs a seed");
-  hipLaunchKernelGGL(embed_fwd_kernel, dim3(ceil_div(a->B * a->T, 4)), dim3(256), 0, stream, *a);
+  hipLaunchKernelGGL(embed_fwd_kernel, dim3(ceil_div(a->B * a->T, 4)), dim3(256), 0, stream, *a, (const int32_t*)nullptr);
+  PH_LAUNCH_CHECK("embed_fwd_kernel");
+  return PH_OK;
+}
+
+extern "C" int ph_embed_fwd_offset(const ph_embed_fwd_args* a, const int32_t* pos_base, hipStream_t stream) {
+  PH_CHECK_ARG(a && a->ids && a->word && a->pos && a->type && a->gamma && a->beta && a->out && pos_base, "ph_embed_fwd_offset: null pointer");
+  ProfScope prof__(PH_FAM_EMBED_CE, 0.0, 0.0, stream);
+  PH_CHECK_ARG(a->H % 4 == 0 && a->H <= MAX_CH * 256 && a->B > 0 && a->T > 0, "ph_embed_fwd_offset: bad dims");
+  PH_CHECK_ARG(!(a->drop_p > 0.f) || a->drop_seed, "ph_embed_fwd_offset: dropout needs a seed");
+  hipLaunchKernelGGL(embed_fwd_kernel, dim3(ceil_div(a->B * a->T, 4)), dim3(256), 0, stream, *a, pos_base);
   PH_LAUNCH_CHECK("embed_fwd_kernel");
   return PH_OK;
 }

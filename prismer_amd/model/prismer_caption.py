@@ -2,18 +2,7 @@
 import torch
 
 from .prismer import Prismer
-
-
-def _first_token_probs(logits_last, first_ids):
-    """softmax(logits, dim=1).index_select(1, first token of every candidate answer) (prismer_caption.py:70, prismer_vqa.py:51) through the
-    library's kernel (ph_softmax_gather_bf16: no stock torch softmax on the rank path, round 6); logits_last: [B, V] view of the decoder's logits"""
-    from .. import ops
-    x = logits_last
-    if x.dtype != torch.bfloat16 or x.stride(-1) != 1 or (x.stride(0) % 8) != 0 or (x.data_ptr() % 16) != 0:
-        x = x.to(torch.bfloat16).contiguous()
-        if x.shape[1] % 8:                                      # (row stride must be a multiple of 8 elements)
-            x = torch.nn.functional.pad(x, (0, 8 - x.shape[1] % 8))[:, :logits_last.shape[1]]
-    return ops.softmax_gather(x, first_ids.to(torch.int64))
+from .rank import rank_answers
 
 
 def tile(x, dim, n_tile):
@@ -77,18 +66,7 @@ class PrismerCaption(Prismer):
             else:
                 s_ids, s_att = self._ids(prefix, device)
             s_ids, s_att = s_ids[:, :-1], s_att[:, :-1]
-            start = self.text_decoder(s_ids, attention_mask=s_att, encoder_hidden_states=experts_train, return_dict=True)
-            prob_first = _first_token_probs(start.logits[:, -1, :], a_ids[:, 0])
-            _, topk_ids = prob_first.topk(k_test, dim=1)
-            ans_ids = torch.cat([a_ids.index_select(0, t) for t in topk_ids], dim=0)
-            ans_att = torch.cat([a_att.index_select(0, t) for t in topk_ids], dim=0)
-            input_ids = torch.cat([tile(s_ids, 0, k_test), ans_ids], dim=1).long()
-            att = torch.cat([tile(s_att, 0, k_test), ans_att], dim=1)
-            enc = tile(experts_train, 0, k_test)
-            targets = input_ids.masked_fill(input_ids == pad, -100)
-            targets[:, :-a_ids.shape[1]] = -100
-            out = self.text_decoder(input_ids, attention_mask=att, encoder_hidden_states=enc, labels=targets, return_dict=True)
-            lp = (-out.loss / torch.sum(targets != -100, dim=-1)).view(-1, k_test)
+            topk_ids, lp = rank_answers(self.text_decoder, experts_train, s_ids, s_att, a_ids, a_att, k_test, pad)
             best = lp.argmax(dim=1)
             if return_scores:                                   # (extension for the parity tests: the candidates and their scores)
                 return topk_ids[best >= 0, best], topk_ids, lp

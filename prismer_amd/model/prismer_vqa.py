@@ -2,7 +2,7 @@
 import torch
 
 from .prismer import Prismer
-from .prismer_caption import tile, _first_token_probs
+from .rank import rank_answers
 
 
 class PrismerVQA(Prismer):
@@ -46,17 +46,7 @@ class PrismerVQA(Prismer):
                 return [self.tokenizer.decode(o[q_ids.shape[1]:], skip_special_tokens=True).lower().strip() for o in out]
             a_ids, a_att = self._ids(answer, device) if not (isinstance(answer, (list, tuple)) and isinstance(answer[0], str)) else \
                 self._ids([' ' + a.capitalize() + '</s>' for a in answer], device, padding='longest', add_special_tokens=False)
-            start = self.text_decoder(q_ids, attention_mask=q_att, encoder_hidden_states=enc, return_dict=True)
-            prob_first = _first_token_probs(start.logits[:, -1, :], a_ids[:, 0])
-            _, topk_ids = prob_first.topk(k_test, dim=1)
-            ans_ids = torch.cat([a_ids.index_select(0, t) for t in topk_ids], dim=0)
-            ans_att = torch.cat([a_att.index_select(0, t) for t in topk_ids], dim=0)
-            input_ids = torch.cat([tile(q_ids, 0, k_test), ans_ids], dim=1).long()
-            att = torch.cat([tile(q_att, 0, k_test), ans_att], dim=1)
-            targets = input_ids.masked_fill(input_ids == pad, -100)
-            targets[:, :-a_ids.shape[1]] = -100
-            out = self.text_decoder(input_ids, attention_mask=att, encoder_hidden_states=tile(enc, 0, k_test), labels=targets, return_dict=True)
-            lp = (-out.loss / torch.sum(targets != -100, dim=-1)).view(-1, k_test)
+            topk_ids, lp = rank_answers(self.text_decoder, enc, q_ids, q_att, a_ids, a_att, k_test, pad)
             best = lp.argmax(dim=1)
             if return_scores:                                   # (extension for the parity tests: the candidates and their scores)
                 return topk_ids[best >= 0, best], topk_ids, lp

@@ -426,6 +426,26 @@ def attention_bwd(d_o, q, k, v, o, lse, B, H, Sq, Sk, dh, *, q_strides, k_stride
     check(lib.ph_attention_bwd(C.byref(a), _stream()), 'ph_attention_bwd')
 
 
+def attention_prefix_fwd(q, pk, pv, ck, cv, R, H, Tc, Tp, group, dh, *, q_strides, pk_strides, pv_strides, ck_strides, cv_strides,
+                         prefix_mask=None, pm_stride=0, cont_mask=None, cm_stride=0, out=None):
+    """shared-prefix attention (ph_attention_prefix_fwd): continuation row r (queries / keys q, ck, cv: [R][Tc]) against the Tp
+    prefix keys of prefix row r // group (pk, pv: [R / group][Tp]) and, causally, its own keys.  Masks: uint8, (batch stride, token
+    stride 1).  Returns o [R*Tc, H*dh] bf16."""
+    if out is None:
+        out = torch.empty((R * Tc, H * dh), dtype=BF16, device=q.device)
+    a = _lib.AttnPrefixFwdArgs()
+    a.q, a.ck, a.cv, a.o = q.data_ptr(), ck.data_ptr(), cv.data_ptr(), out.data_ptr()
+    a.pk, a.pv = (pk.data_ptr(), pv.data_ptr()) if Tp > 0 else (None, None)
+    (a.q_bs, a.q_ts), (a.pk_bs, a.pk_ts), (a.pv_bs, a.pv_ts) = q_strides, pk_strides, pv_strides
+    (a.ck_bs, a.ck_ts), (a.cv_bs, a.cv_ts), (a.o_bs, a.o_ts) = ck_strides, cv_strides, (Tc * H * dh, H * dh)
+    a.prefix_mask, a.pm_bs = ptr(prefix_mask), pm_stride
+    a.cont_mask, a.cm_bs = ptr(cont_mask), cm_stride
+    a.R, a.group, a.H, a.Tc, a.Tp, a.dh = R, group, H, Tc, Tp, dh
+    a.scale = dh ** -0.5
+    check(lib.ph_attention_prefix_fwd(C.byref(a), _stream()), 'ph_attention_prefix_fwd')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- front end
 
 def patchify(img, p, Kp):
@@ -660,7 +680,9 @@ def embed_args(ids, word, pos, typ, gamma, beta, eps, pad_id, out, xhat, rstd, d
     return a
 
 
-def embed_fwd(ids, word, pos, typ, gamma, beta, eps, pad_id, drop=None, want_f32=False):
+def embed_fwd(ids, word, pos, typ, gamma, beta, eps, pad_id, drop=None, want_f32=False, pos_base=None):
+    """pos_base: int32 [B] device tensor or None -- the offset form (ph_embed_fwd_offset): real tokens of row b take position
+    pad + pos_base[b] + cumsum(ids != pad)"""
     B, T = ids.shape
     H = word.shape[1]
     out = torch.empty((B * T, H), dtype=BF16, device=ids.device)
@@ -668,7 +690,11 @@ def embed_fwd(ids, word, pos, typ, gamma, beta, eps, pad_id, drop=None, want_f32
     rstd = torch.empty((B * T,), dtype=F32, device=ids.device)
     out_f32 = torch.empty((B * T, H), dtype=F32, device=ids.device) if want_f32 else None
     a = embed_args(ids, word, pos, typ, gamma, beta, eps, pad_id, out, xhat, rstd, drop, out_f32)
-    check(lib.ph_embed_fwd(C.byref(a), _stream()), 'ph_embed_fwd')
+    if pos_base is None:
+        check(lib.ph_embed_fwd(C.byref(a), _stream()), 'ph_embed_fwd')
+    else:
+        assert pos_base.dtype == torch.int32 and pos_base.numel() == B and pos_base.is_contiguous()
+        check(lib.ph_embed_fwd_offset(C.byref(a), pos_base.data_ptr(), _stream()), 'ph_embed_fwd_offset')
     if want_f32:
         return out, xhat, rstd, out_f32
     return out, xhat, rstd

@@ -336,6 +336,7 @@ class DecoderProgram:
         h, hf = self._self_attn_cached(F_['sa'], F_['idx'], len(self.layers), h, hf, st, t0, T, key_mask)
         h, hf = self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, None, None)
         st['filled'] = max(st['filled'], T)
+        st['key_mask'] = key_mask                                                # (the prefix key mask of score_continuations)
         last = h if Sq == 1 else h.view(Bb, Sq, H)[:, -1].contiguous()           # LM head on the last position only
         t0_ = self.head_dense.fwd(last, act=ACT_GELU)
         t1, _, _ = self.head_ln.fwd(t0_, save_stats=False)
@@ -343,6 +344,58 @@ class DecoderProgram:
         logits = torch.empty(Bb, self.Vpad, dtype=BF16, device=h.device)
         ops.gemm(t1, P.w(e + 'word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=V)
         return logits[:, :V]
+
+    # ---------------------------------------------------------------------------------------- shared-prefix scoring
+    # inference='rank' (prismer_caption.py:59-112, prismer_vqa.py:64-113) runs [prompt || candidate] for k candidates of every image.  Causal
+    # attention makes the prompt's hidden states the same for all k, so the prompt runs ONCE (decode_begin + the prefill decode: per-layer
+    # self-attention K/V cache, cross-attention K/V projected once per image) and only the continuations run per candidate: their
+    # self-attention reads the cached prefix K/V of their image (ph_attention_prefix_fwd, nothing copied k times), their cross-attention
+    # reads the image's K/V with the k*Tc continuation tokens of the image as one query block.
+    def _self_attn_shared(self, blk, slot, h, hf, st, R, Tc, Tp, group, cont_mask):
+        d = self.d
+        H, nh = d.hidden_size, d.num_attention_heads
+        dh = H // nh
+        Tmax = st['Tmax']
+        qkv = blk['qkv'].fwd(h)                                                  # [R*Tc, 3H]
+        cache = st['cache'][st['cur']][slot]                                     # [images, Tmax, 2H]: prefix K | V
+        pm = st.get('key_mask')
+        cs, qs = (Tmax * 2 * H, 2 * H), (Tc * 3 * H, 3 * H)
+        o = ops.attention_prefix_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], qkv[:, H:2 * H], qkv[:, 2 * H:], R, nh, Tc, Tp, group, dh,
+                                     q_strides=qs, pk_strides=cs, pv_strides=cs, ck_strides=qs, cv_strides=qs,
+                                     prefix_mask=pm, pm_stride=0 if pm is None else pm.stride(0), cont_mask=cont_mask, cm_stride=Tc)
+        s = blk['out'].fwd(o, residual=hf, out_f32=True)
+        y, yf, _, _ = self.post_ln(blk['ln'], s)
+        return y, yf
+
+    def score_continuations(self, st, cont_ids, cont_att, labels, pos_base, Tp, group):
+        """Per-row loss [R] fp32 (the summed, shifted, label-smoothed CE of `forward`) of R = images * group continuation rows
+        cont_ids [R, Tc] (row r continues prefix row r // group of the state `decode_begin` + the prefill `decode` produced) under
+        cont_att [R, Tc] and labels [R, Tc] (-100 = not scored).  The continuation attends to the prefix positions 0 .. Tp-1 (prefix key
+        mask of the prefill) and, causally, to itself; real tokens take positions pad + pos_base[r] + cumsum(cont_ids != pad)."""
+        d, P = self.d, self.P
+        R, Tc = cont_ids.shape
+        B, S = st['Bb'], st['S']
+        assert R == B * group and 0 <= Tp <= st['filled'], 'score_continuations: group rows per prefix row, Tp within the prefill'
+        e = 'roberta.embeddings.'
+        cont_mask = (cont_att != 0).to(torch.uint8).contiguous()
+        h, _, _, hf = ops.embed_fwd(cont_ids.contiguous(), P.f(e + 'word_embeddings.weight'), P.f(e + 'position_embeddings.weight'),
+                                    P.f(e + 'token_type_embeddings.weight'), P.f(e + 'LayerNorm.weight'), P.f(e + 'LayerNorm.bias'),
+                                    d.layer_norm_eps, d.pad_token_id, None, want_f32=True, pos_base=pos_base.to(torch.int32).contiguous())
+        for i, L in enumerate(self.layers):
+            h, hf = self._self_attn_shared(L['sa'], i, h, hf, st, R, Tc, Tp, group, cont_mask)
+            h, hf = self.cross_attn_fwd(L['ca'], L['idx'], h, hf, None, B, group * Tc, S, None, None, st['kvs'][i])
+            h, hf = self.adaptor_fwd(L['ad'], h, hf, None)
+            h, hf = self.mlp_fwd(L['mlp'], L['idx'], h, hf, None, None)
+        F_ = self.final
+        h, hf = self._self_attn_shared(F_['sa'], len(self.layers), h, hf, st, R, Tc, Tp, group, cont_mask)
+        h, hf = self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, None, None)
+        t0 = self.head_dense.fwd(h, act=ACT_GELU)
+        t1, _, _ = self.head_ln.fwd(t0, save_stats=False)
+        V = d.vocab_size
+        logits = torch.empty(R * Tc, self.Vpad, dtype=BF16, device=h.device)
+        ops.gemm(t1, P.w(e + 'word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=V)
+        loss, _ = ops.ce_fwd(logits, labels.contiguous(), R, Tc, V, d.label_smoothing)
+        return loss
 
     def backward(self, sv, dloss):
         """dloss: fp32 [B] gradient of the per-sample losses. Returns d(enc) as bf16 [B, S, Hv]."""
