@@ -17,7 +17,7 @@
 #include <float.h>
 #include <algorithm>
 #include <mutex>
-#include <unordered_map>
+#include <map>
 #include <type_traits>
 #include <utility>
 #include <stdlib.h>
@@ -1189,7 +1189,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW / 2,
 // re-reads everything), 12-17 us per launch for a few MFLOP (0.016-0.028 of the MFMA peak, 75 launches = 1.08 ms per step).
 // Here ONE block owns a (batch, head) pair and EVERY wave owns ALL queries (QT 16-query sub-tiles): the four waves split the KEYS in 32-key
 // units (unit u -> wave u % 4), so the key sequence is walked four units at a time, and the partial results are merged through LDS:
-//   forward : per wave running (max, sum, O^T) over its units, merged like split-K flash decoding;
+//   forward : per wave running (max, sum, O^T) over its units, merged like split-K flash decoding (sm_fwd_unit, sm_fwd_store_single and
+//             sm_fwd_merge_store: the shared-prefix kernel of rank inference runs the same three on its own prologue);
 //   backward: ONE launch for dQ, dK and dV.  Sweep 0 = delta (fp32, from the same recomputed P / dP as sweep 1, see attn_bwd_dq_kernel),
 //             merged over the waves; sweep 1 per unit = the dQ role (S^T = K Q^T orientation, dQ^T += K^T dS^T, merged at the end) and
 //             the dK / dV role (mirror orientation S = Q K^T with one key per lane: every wave sees all queries, so dK / dV of its keys
@@ -1230,163 +1231,128 @@ __device__ __forceinline__ void sm_stage(bf16* img, const bf16* src, int64_t ts,
     }
 }
 
-template <int QT>
-__global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a) {
-  constexpr int DH = 64;
-  using C = Cfg<DH>;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = lane & 15, g = lane >> 4;
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
-  const int nunits = (a.Sk + 31) >> 5, rows_pad = nunits * 32;
-  bf16* vimg = reinterpret_cast<bf16*>(smem_raw);
-  float* kst = reinterpret_cast<float*>(vimg + rows_pad * C::RS);
-  float* obuf = reinterpret_cast<float*>(smem_raw);                         // merge images alias the V image (two barriers apart)
-  float* mbuf = obuf + 4 * QT * 16 * SM_OS;
-  float* lbuf = mbuf + 4 * QT * 16;
-  const bf16* Q = reinterpret_cast<const bf16*>(a.q) + b * a.q_bs + (int64_t)h * DH;
-  const bf16* K = reinterpret_cast<const bf16*>(a.k) + b * a.k_bs + (int64_t)h * DH;
-  const bf16* V = reinterpret_cast<const bf16*>(a.v) + b * a.v_bs + (int64_t)h * DH;
-  const uint8_t* km = a.key_mask ? a.key_mask + (int64_t)b * a.Sk : nullptr;
-
-  int qi[QT];
-  bf16x8 qf[QT][C::KS];
-  f32x4 o[QT][C::DT];
-  float m[QT], lsum[QT];
-  uint32_t rowid[QT];
+// ---- the small-query forward, written once: attn_fwd_small_kernel and attn_prefix_fwd_kernel differ in their prologues only (where K / V rows
+// and key states come from); the unit step, the one-unit store and the merge below are shared.
+//
+// One 32-key unit: S^T = K Q^T (lane = query column), score_of, running (max, sum) with the alpha rescale of O^T, probability dropout,
+// O^T += V^T P^T (V read transposed from the LDS image at row kbase).  kf: the unit's K row fragments; kst: key states, indexed like the V
+// image; causal: the unit has a causal cut, its key j then has causal index causal_k0 + j (a wave-uniform flag, so a unit without a cut pays no
+// per-element compare); dr is read only when DROP.
+template <int QT> struct SmDrop { bool on; DropCtx dc; uint32_t rowid[QT]; };      // probability dropout of a launch: generator row per query
+template <int QT, bool DROP>
+__device__ __forceinline__ void sm_fwd_unit(const bf16x8 (&kf)[2][Cfg<64>::KS], const bf16x8 (&qf)[QT][Cfg<64>::KS], const int (&qi)[QT],
+                                            const bf16* vimg, const float* kst, int kbase, bool causal, int causal_k0, float scale, float (&m)[QT],
+                                            float (&lsum)[QT], f32x4 (&o)[QT][Cfg<64>::DT], const SmDrop<QT>& dr) {
+  using C = Cfg<64>;
+  const int lane = threadIdx.x & 63, g = lane >> 4;
+  f32x4 s[QT][2];
+  float mx[QT];
 #pragma unroll
-  for (int t = 0; t < QT; ++t) {
-    qi[t] = t * 16 + c;
-    const int qr = qi[t] < a.Sq ? qi[t] : a.Sq - 1;
+  for (int t = 0; t < QT; ++t) mx[t] = -INFINITY;
 #pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) qf[t][ks] = *reinterpret_cast<const bf16x8*>(Q + (int64_t)qr * a.q_ts + ks * 32 + g * 8);
+  for (int nt = 0; nt < 2; ++nt) {
+    f32x4 acc[QT];
 #pragma unroll
-    for (int d = 0; d < C::DT; ++d) o[t][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    m[t] = NEG_MASK; lsum[t] = 0.f;
-    rowid[t] = (uint32_t)((b * a.H + h) * a.Sq + qr);
-  }
-  // K row fragments of ALL this wave's units straight from global memory (rows beyond Sk re-read the last key; masked by index below):
-  // one round of global latency for the whole kernel
-  bf16x8 kfu[SM_MAXU][2][C::KS];
+    for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ui = 0; ui < SM_MAXU; ++ui)
-    if (wave + 4 * ui < nunits) {
+    for (int ks = 0; ks < C::KS; ++ks)
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int kr = min((wave + 4 * ui) * 32 + nt * 16 + c, a.Sk - 1);
-#pragma unroll
-        for (int ks = 0; ks < C::KS; ++ks) kfu[ui][nt][ks] = *reinterpret_cast<const bf16x8*>(K + (int64_t)kr * a.k_ts + ks * 32 + g * 8);
-      }
-    }
-  sm_stage<SM_MAX_UNITS>(vimg, V, a.v_ts, a.Sk, rows_pad);
-  for (int i = threadIdx.x; i < rows_pad; i += 256) kst[i] = key_state(key_raw(km, i, a.Sk), i, a.Sk);
-  DropCtx dc;
-  const bool drop = a.drop_p > 0.f;
-  if (drop) dc = make_drop(a.drop_seed, a.drop_stream, a.drop_p);
-#pragma unroll
-  for (int t = 0; t < QT; ++t)
-#pragma unroll
-    for (int ks = 0; ks < C::KS; ++ks) settle(qf[t][ks]);
-  __syncthreads();
-
-#pragma unroll
-  for (int ui = 0; ui < SM_MAXU; ++ui) {
-    if (wave + 4 * ui >= nunits) break;
-    const int kbase = (wave + 4 * ui) * 32;
-    f32x4 s[QT][2];
-    float mx[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) mx[t] = -INFINITY;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      f32x4 acc[QT];
-#pragma unroll
-      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < C::KS; ++ks)
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfu[ui][nt][ks], qf[t][ks], acc[t], 0, 0, 0);
-      const f32x4 st = *reinterpret_cast<const f32x4*>(kst + kbase + nt * 16 + g * 4);
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ki = kbase + nt * 16 + g * 4 + r;
-          acc[t][r] = score_of(acc[t][r], a.scale, st[r], a.causal && ki > qi[t]);
-          mx[t] = fmaxf(mx[t], acc[t][r]);
-        }
-        s[t][nt] = acc[t];
-      }
-    }
+      for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[nt][ks], qf[t][ks], acc[t], 0, 0, 0);
+    const f32x4 st = *reinterpret_cast<const f32x4*>(kst + kbase + nt * 16 + g * 4);
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
-      const float m_new = fmaxf(m[t], xor_max(mx[t]));
-      const float alpha = __expf(m[t] - m_new);
-      float rs = 0.f;
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
+      for (int r = 0; r < 4; ++r) {
+        const int ki = causal_k0 + nt * 16 + g * 4 + r;
+        acc[t][r] = score_of(acc[t][r], scale, st[r], causal && ki > qi[t]);
+        mx[t] = fmaxf(mx[t], acc[t][r]);
+      }
+      s[t][nt] = acc[t];
+    }
+  }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = __expf(s[t][nt][r] - m_new);
-          rs += p;
-          s[t][nt][r] = p;
-        }
-      rs = xor_sum(rs);
-      lsum[t] = lsum[t] * alpha + rs;
-      m[t] = m_new;
+  for (int t = 0; t < QT; ++t) {
+    const float m_new = fmaxf(m[t], xor_max(mx[t]));
+    const float alpha = __expf(m[t] - m_new);
+    float rs = 0.f;
 #pragma unroll
-      for (int d = 0; d < C::DT; ++d) o[t][d] *= alpha;
-      if (drop) {
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(s[t][nt][r] - m_new);
+        rs += p;
+        s[t][nt][r] = p;
+      }
+    rs = xor_sum(rs);
+    lsum[t] = lsum[t] * alpha + rs;
+    m[t] = m_new;
+#pragma unroll
+    for (int d = 0; d < C::DT; ++d) o[t][d] *= alpha;
+    if constexpr (DROP) {
+      if (dr.on) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
-          const u32x4 rnd = philox4x32((uint32_t)((kbase + nt * 16 + g * 4) >> 2), rowid[t], dc.stream, 0xa77eu, dc.k0, dc.k1);
+          const u32x4 rnd = philox4x32((uint32_t)((kbase + nt * 16 + g * 4) >> 2), dr.rowid[t], dr.dc.stream, 0xa77eu, dr.dc.k0, dr.dc.k1);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) s[t][nt][r] = drop_apply(dc, rnd[r], s[t][nt][r]);
+          for (int r = 0; r < 4; ++r) s[t][nt][r] = drop_apply(dr.dc, rnd[r], s[t][nt][r]);
         }
       }
     }
-    bf16x8 pf[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) pf[t] = pack2(s[t][0], s[t][1]);
-#pragma unroll
-    for (int d = 0; d < C::DT; ++d) {
-      const bf16x8 vfr = frag_tr<DH>(vimg, kbase, d * 16, lane);
-#pragma unroll
-      for (int t = 0; t < QT; ++t) o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr, pf[t], o[t][d], 0, 0, 0);
-    }
   }
-  // ---- one unit (self-attention at T <= 32): wave 0 holds the whole result
-  if (nunits == 1) {
-    if (wave == 0) {
+  bf16x8 pf[QT];
 #pragma unroll
-      for (int t = 0; t < QT; ++t)
-        if (qi[t] < a.Sq) {
-          const float inv = 1.0f / lsum[t];
-          bf16* O = reinterpret_cast<bf16*>(a.o) + b * a.o_bs + (int64_t)qi[t] * a.o_ts + (int64_t)h * DH;
+  for (int t = 0; t < QT; ++t) pf[t] = pack2(s[t][0], s[t][1]);
 #pragma unroll
-          for (int d = 0; d < C::DT; ++d) {
-            const bf16x4 tt = {f2bf(o[t][d][0] * inv), f2bf(o[t][d][1] * inv), f2bf(o[t][d][2] * inv), f2bf(o[t][d][3] * inv)};
-            *reinterpret_cast<bf16x4*>(O + d * 16 + g * 4) = tt;
-          }
-          if (g == 0 && a.lse) a.lse[(int64_t)(b * a.H + h) * a.Sq + qi[t]] = m[t] + __logf(lsum[t]);
-        }
-    }
-    return;
+  for (int d = 0; d < C::DT; ++d) {
+    const bf16x8 vfr = frag_tr<64>(vimg, kbase, d * 16, lane);
+#pragma unroll
+    for (int t = 0; t < QT; ++t) o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr, pf[t], o[t][d], 0, 0, 0);
   }
-  // ---- merge the (max, sum, O^T) partials of the waves that held units
-  __syncthreads();                                          // every wave is done with the V image / key states: the merge images may overwrite them
+}
+
+// One unit in the whole launch: wave 0 holds the result.  O: the (batch, head) slice of the output, row stride o_ts; lse: its nq entries or null.
+template <int QT>
+__device__ __forceinline__ void sm_fwd_store_single(const int (&qi)[QT], int nq, const float (&m)[QT], const float (&lsum)[QT],
+                                                    const f32x4 (&o)[QT][Cfg<64>::DT], bf16* O, int64_t o_ts, float* lse) {
+  const int g = (threadIdx.x & 63) >> 4;
+  if (threadIdx.x >> 6) return;
+#pragma unroll
+  for (int t = 0; t < QT; ++t)
+    if (qi[t] < nq) {
+      const float inv = 1.0f / lsum[t];
+      bf16* Or = O + (int64_t)qi[t] * o_ts;
+#pragma unroll
+      for (int d = 0; d < Cfg<64>::DT; ++d) {
+        const bf16x4 tt = {f2bf(o[t][d][0] * inv), f2bf(o[t][d][1] * inv), f2bf(o[t][d][2] * inv), f2bf(o[t][d][3] * inv)};
+        *reinterpret_cast<bf16x4*>(Or + d * 16 + g * 4) = tt;
+      }
+      if (g == 0 && lse) lse[qi[t]] = m[t] + __logf(lsum[t]);
+    }
+}
+
+// Merge of the (max, sum, O^T) partials of the waves that held units, like split-K flash decoding, and the final store.  The merge images
+// (smem) alias the V image and the key states: the first barrier is where every wave is done with those.
+template <int QT>
+__device__ __forceinline__ void sm_fwd_merge_store(char* smem, int nunits, int nq, const float (&m)[QT], const float (&lsum)[QT],
+                                                   const f32x4 (&o)[QT][Cfg<64>::DT], bf16* O, int64_t o_ts, float* lse) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  float* obuf = reinterpret_cast<float*>(smem);
+  float* mbuf = obuf + 4 * QT * 16 * SM_OS;
+  float* lbuf = mbuf + 4 * QT * 16;
+  __syncthreads();
   if (wave < nunits) {
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
       const int q = t * 16 + c;
       if (g == 0) { mbuf[wave * QT * 16 + q] = m[t]; lbuf[wave * QT * 16 + q] = lsum[t]; }
 #pragma unroll
-      for (int d = 0; d < C::DT; ++d) *reinterpret_cast<f32x4*>(obuf + (wave * QT * 16 + q) * SM_OS + d * 16 + g * 4) = o[t][d];
+      for (int d = 0; d < Cfg<64>::DT; ++d) *reinterpret_cast<f32x4*>(obuf + (wave * QT * 16 + q) * SM_OS + d * 16 + g * 4) = o[t][d];
     }
   }
   __syncthreads();
   const int q = threadIdx.x >> 2, col = (threadIdx.x & 3) * 16;
-  if (q < a.Sq && q < QT * 16) {
+  if (q < nq && q < QT * 16) {
     const int nw = nunits < 4 ? nunits : 4;
     float M = NEG_MASK;
     for (int w = 0; w < nw; ++w) M = fmaxf(M, mbuf[w * QT * 16 + q]);
@@ -1406,14 +1372,81 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a)
       }
     }
     const float inv = 1.0f / L;
-    bf16* O = reinterpret_cast<bf16*>(a.o) + b * a.o_bs + (int64_t)q * a.o_ts + (int64_t)h * DH + col;
+    bf16* Or = O + (int64_t)q * o_ts + col;
     bf16x8 o0, o1;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { o0[j] = f2bf(acc[j] * inv); o1[j] = f2bf(acc[8 + j] * inv); }
-    *reinterpret_cast<bf16x8*>(O) = o0;
-    *reinterpret_cast<bf16x8*>(O + 8) = o1;
-    if ((threadIdx.x & 3) == 0 && a.lse) a.lse[(int64_t)(b * a.H + h) * a.Sq + q] = M + __logf(L);
+    *reinterpret_cast<bf16x8*>(Or) = o0;
+    *reinterpret_cast<bf16x8*>(Or + 8) = o1;
+    if ((threadIdx.x & 3) == 0 && lse) lse[q] = M + __logf(L);
   }
+}
+
+template <int QT>
+__global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a) {
+  constexpr int DH = 64;
+  using C = Cfg<DH>;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+  const int nunits = (a.Sk + 31) >> 5, rows_pad = nunits * 32;
+  bf16* vimg = reinterpret_cast<bf16*>(smem_raw);
+  float* kst = reinterpret_cast<float*>(vimg + rows_pad * C::RS);
+  const bf16* Q = reinterpret_cast<const bf16*>(a.q) + b * a.q_bs + (int64_t)h * DH;
+  const bf16* K = reinterpret_cast<const bf16*>(a.k) + b * a.k_bs + (int64_t)h * DH;
+  const bf16* V = reinterpret_cast<const bf16*>(a.v) + b * a.v_bs + (int64_t)h * DH;
+  bf16* O = reinterpret_cast<bf16*>(a.o) + b * a.o_bs + (int64_t)h * DH;
+  float* lse = a.lse ? a.lse + (int64_t)(b * a.H + h) * a.Sq : nullptr;
+  const uint8_t* km = a.key_mask ? a.key_mask + (int64_t)b * a.Sk : nullptr;
+
+  int qi[QT];
+  bf16x8 qf[QT][C::KS];
+  f32x4 o[QT][C::DT];
+  float m[QT], lsum[QT];
+  SmDrop<QT> dr;
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    qi[t] = t * 16 + c;
+    const int qr = qi[t] < a.Sq ? qi[t] : a.Sq - 1;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) qf[t][ks] = *reinterpret_cast<const bf16x8*>(Q + (int64_t)qr * a.q_ts + ks * 32 + g * 8);
+#pragma unroll
+    for (int d = 0; d < C::DT; ++d) o[t][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    m[t] = NEG_MASK; lsum[t] = 0.f;
+    dr.rowid[t] = (uint32_t)((b * a.H + h) * a.Sq + qr);
+  }
+  // K row fragments of ALL this wave's units straight from global memory (rows beyond Sk re-read the last key; masked by index below):
+  // one round of global latency for the whole kernel
+  bf16x8 kfu[SM_MAXU][2][C::KS];
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui)
+    if (wave + 4 * ui < nunits) {
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int kr = min((wave + 4 * ui) * 32 + nt * 16 + c, a.Sk - 1);
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) kfu[ui][nt][ks] = *reinterpret_cast<const bf16x8*>(K + (int64_t)kr * a.k_ts + ks * 32 + g * 8);
+      }
+    }
+  sm_stage<SM_MAX_UNITS>(vimg, V, a.v_ts, a.Sk, rows_pad);
+  for (int i = threadIdx.x; i < rows_pad; i += 256) kst[i] = key_state(key_raw(km, i, a.Sk), i, a.Sk);
+  dr.on = a.drop_p > 0.f;
+  if (dr.on) dr.dc = make_drop(a.drop_seed, a.drop_stream, a.drop_p);
+#pragma unroll
+  for (int t = 0; t < QT; ++t)
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks) settle(qf[t][ks]);
+  __syncthreads();
+
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui) {
+    if (wave + 4 * ui >= nunits) break;
+    const int kbase = (wave + 4 * ui) * 32;
+    sm_fwd_unit<QT, true>(kfu[ui], qf, qi, vimg, kst, kbase, a.causal, kbase, a.scale, m, lsum, o, dr);
+  }
+  if (nunits == 1) sm_fwd_store_single<QT>(qi, a.Sq, m, lsum, o, O, a.o_ts, lse);       // (self-attention at T <= 32)
+  else sm_fwd_merge_store<QT>(smem_raw, nunits, a.Sq, m, lsum, o, O, a.o_ts, lse);
 }
 
 // Shared-prefix forward (rank inference, model/prismer_caption.py:59-112 and model/prismer_vqa.py:64-113 without the k-fold tiling): attn_fwd_small_kernel
@@ -1432,14 +1465,12 @@ __global__ __launch_bounds__(256) void attn_prefix_fwd_kernel(ph_attn_prefix_fwd
   const int np = (a.Tp + 31) >> 5, nunits = np + 1, rows_pad = nunits * 32;
   bf16* vimg = reinterpret_cast<bf16*>(smem_raw);
   float* kst = reinterpret_cast<float*>(vimg + rows_pad * C::RS);
-  float* obuf = reinterpret_cast<float*>(smem_raw);                         // merge images alias the V image (two barriers apart)
-  float* mbuf = obuf + 4 * QT * 16 * SM_OS;
-  float* lbuf = mbuf + 4 * QT * 16;
   const bf16* Q = reinterpret_cast<const bf16*>(a.q) + r * a.q_bs + (int64_t)h * DH;
   const bf16* PK = np ? reinterpret_cast<const bf16*>(a.pk) + pr * a.pk_bs + (int64_t)h * DH : nullptr;
   const bf16* PV = np ? reinterpret_cast<const bf16*>(a.pv) + pr * a.pv_bs + (int64_t)h * DH : nullptr;
   const bf16* CK = reinterpret_cast<const bf16*>(a.ck) + r * a.ck_bs + (int64_t)h * DH;
   const bf16* CV = reinterpret_cast<const bf16*>(a.cv) + r * a.cv_bs + (int64_t)h * DH;
+  bf16* O = reinterpret_cast<bf16*>(a.o) + r * a.o_bs + (int64_t)h * DH;
   const uint8_t* pm = (np && a.prefix_mask) ? a.prefix_mask + pr * a.pm_bs : nullptr;
   const uint8_t* cm = a.cont_mask ? a.cont_mask + r * a.cm_bs : nullptr;
 
@@ -1491,119 +1522,10 @@ __global__ __launch_bounds__(256) void attn_prefix_fwd_kernel(ph_attn_prefix_fwd
   for (int ui = 0; ui < SM_MAXU; ++ui) {
     const int u = wave + 4 * ui;
     if (u >= nunits) break;
-    const int kbase = u * 32;
-    const bool cont = u == np;
-    f32x4 s[QT][2];
-    float mx[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) mx[t] = -INFINITY;
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      f32x4 acc[QT];
-#pragma unroll
-      for (int t = 0; t < QT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < C::KS; ++ks)
-#pragma unroll
-        for (int t = 0; t < QT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfu[ui][nt][ks], qf[t][ks], acc[t], 0, 0, 0);
-      const f32x4 st = *reinterpret_cast<const f32x4*>(kst + kbase + nt * 16 + g * 4);
-#pragma unroll
-      for (int t = 0; t < QT; ++t) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const int kj = nt * 16 + g * 4 + rr;                                 // key index inside the unit
-          acc[t][rr] = score_of(acc[t][rr], a.scale, st[rr], cont && kj > qi[t]);
-          mx[t] = fmaxf(mx[t], acc[t][rr]);
-        }
-        s[t][nt] = acc[t];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const float m_new = fmaxf(m[t], xor_max(mx[t]));
-      const float alpha = __expf(m[t] - m_new);
-      float rs = 0.f;
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float p = __expf(s[t][nt][rr] - m_new);
-          rs += p;
-          s[t][nt][rr] = p;
-        }
-      rs = xor_sum(rs);
-      lsum[t] = lsum[t] * alpha + rs;
-      m[t] = m_new;
-#pragma unroll
-      for (int d = 0; d < C::DT; ++d) o[t][d] *= alpha;
-    }
-    bf16x8 pf[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) pf[t] = pack2(s[t][0], s[t][1]);
-#pragma unroll
-    for (int d = 0; d < C::DT; ++d) {
-      const bf16x8 vfr = frag_tr<DH>(vimg, kbase, d * 16, lane);
-#pragma unroll
-      for (int t = 0; t < QT; ++t) o[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfr, pf[t], o[t][d], 0, 0, 0);
-    }
+    sm_fwd_unit<QT, false>(kfu[ui], qf, qi, vimg, kst, u * 32, u == np, 0, a.scale, m, lsum, o, SmDrop<QT>{});
   }
-  // ---- no prefix (Tp = 0): wave 0 holds the whole result
-  if (nunits == 1) {
-    if (wave == 0) {
-#pragma unroll
-      for (int t = 0; t < QT; ++t)
-        if (qi[t] < a.Tc) {
-          const float inv = 1.0f / lsum[t];
-          bf16* O = reinterpret_cast<bf16*>(a.o) + r * a.o_bs + (int64_t)qi[t] * a.o_ts + (int64_t)h * DH;
-#pragma unroll
-          for (int d = 0; d < C::DT; ++d) {
-            const bf16x4 tt = {f2bf(o[t][d][0] * inv), f2bf(o[t][d][1] * inv), f2bf(o[t][d][2] * inv), f2bf(o[t][d][3] * inv)};
-            *reinterpret_cast<bf16x4*>(O + d * 16 + g * 4) = tt;
-          }
-        }
-    }
-    return;
-  }
-  // ---- merge the (max, sum, O^T) partials of the waves that held units (as attn_fwd_small_kernel)
-  __syncthreads();
-  if (wave < nunits) {
-#pragma unroll
-    for (int t = 0; t < QT; ++t) {
-      const int q = t * 16 + c;
-      if (g == 0) { mbuf[wave * QT * 16 + q] = m[t]; lbuf[wave * QT * 16 + q] = lsum[t]; }
-#pragma unroll
-      for (int d = 0; d < C::DT; ++d) *reinterpret_cast<f32x4*>(obuf + (wave * QT * 16 + q) * SM_OS + d * 16 + g * 4) = o[t][d];
-    }
-  }
-  __syncthreads();
-  const int q = threadIdx.x >> 2, col = (threadIdx.x & 3) * 16;
-  if (q < a.Tc) {
-    const int nw = nunits < 4 ? nunits : 4;
-    float M = NEG_MASK;
-    for (int w = 0; w < nw; ++w) M = fmaxf(M, mbuf[w * QT * 16 + q]);
-    float L = 0.f;
-    float acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = 0.f;
-    for (int w = 0; w < nw; ++w) {
-      const float wgt = __expf(mbuf[w * QT * 16 + q] - M);
-      L += wgt * lbuf[w * QT * 16 + q];
-      const float* src = obuf + (w * QT * 16 + q) * SM_OS + col;
-#pragma unroll
-      for (int j4 = 0; j4 < 4; ++j4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(src + j4 * 4);
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) acc[j4 * 4 + rr] += wgt * v[rr];
-      }
-    }
-    const float inv = 1.0f / L;
-    bf16* O = reinterpret_cast<bf16*>(a.o) + r * a.o_bs + (int64_t)q * a.o_ts + (int64_t)h * DH + col;
-    bf16x8 o0, o1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { o0[j] = f2bf(acc[j] * inv); o1[j] = f2bf(acc[8 + j] * inv); }
-    *reinterpret_cast<bf16x8*>(O) = o0;
-    *reinterpret_cast<bf16x8*>(O + 8) = o1;
-  }
+  if (nunits == 1) sm_fwd_store_single<QT>(qi, a.Tc, m, lsum, o, O, a.o_ts, nullptr);   // (no prefix: Tp = 0)
+  else sm_fwd_merge_store<QT>(smem_raw, nunits, a.Tc, m, lsum, o, O, a.o_ts, nullptr);
 }
 
 // Backward of a (batch, head) pair in ONE launch and ONE pass of the generator / exponentials (second version, round 5: the first one
@@ -1890,14 +1812,17 @@ int attn_qt2_ok() { return 1; }          // 1 = by sequence length (0 = never an
 
 template <typename KernelT>
 int set_smem(KernelT k, int bytes) {
-  // the attribute is raised only when a launch needs more than any earlier launch of THAT kernel did (the call costs host time on every
-  // eager launch otherwise; round-5 advisor finding).  Keyed by the kernel's address: KernelT is the same type for every kernel of one signature.
+  // the attribute is raised only when a launch needs more than any earlier launch of THAT kernel on THAT device did (the call costs host time
+  // on every eager launch otherwise; round-5 advisor finding).  The attribute is per device, so the cache is keyed by (device, kernel address):
+  // KernelT is the same type for every kernel of one signature.  Launches within the 48 KB default make no runtime call at all.
   if (bytes <= 48 * 1024) return bytes;
   static std::mutex mu;
-  static std::unordered_map<const void*, int> largest;
+  static std::map<std::pair<int, const void*>, int> largest;
   const void* key = reinterpret_cast<const void*>(k);
+  int dev = 0;
+  hipGetDevice(&dev);
   std::lock_guard<std::mutex> lock(mu);
-  int& cur = largest[key];
+  int& cur = largest[{dev, key}];
   if (bytes > cur) {
     hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     cur = bytes;

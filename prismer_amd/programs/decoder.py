@@ -84,15 +84,13 @@ class DecoderProgram:
         y, m, r = ln.fwd(s, out_f32=yf)
         return y, yf, m, r
 
-    def self_attn_fwd(self, blk, li, h, hf, B, T, key_mask, seed, sv):
+    def self_attn_fwd(self, blk, li, h, hf, attend, seed, sv):
+        """qkv GEMM -> attend(li, qkv) = (o, lse, dropout descriptor of the probabilities) -> out-projection with residual -> LayerNorm.
+        The caller's `attend` says what the queries see: the packed sequence itself (forward), the K/V cache (decode) or a shared
+        prefix plus the row's own keys (score_continuations)."""
         d = self.d
-        H, nh = d.hidden_size, d.num_attention_heads
-        dh = H // nh
         qkv = blk['qkv'].fwd(h)
-        st = (T * 3 * H, 3 * H)
-        dr_a = self.drop(li * 16 + 1, d.attention_probs_dropout_prob, seed)
-        o, lse = ops.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, nh, T, T, dh, q_strides=st, k_strides=st, v_strides=st,
-                                   key_mask=key_mask, causal=True, drop=dr_a)
+        o, lse, dr_a = attend(li, qkv)
         dr_h = self.drop(li * 16 + 2, d.hidden_dropout_prob, seed)
         s = blk['out'].fwd(o, drop=dr_h, residual=hf, out_f32=True)
         y, yf, m, r = self.post_ln(blk['ln'], s)
@@ -196,70 +194,99 @@ class DecoderProgram:
         return blk['inter'].dgrad(dipre, residual=ds)
 
     # ---------------------------------------------------------------------------------------- whole decoder
-    def forward(self, input_ids, attention_mask, enc, labels, seed, save, want_logits=True):
-        """enc: [B, S, Hv] bf16 contiguous. seed: int64[1] device tensor or None (no dropout = eval mode).
-        Returns (logits_buf [B*T, Vpad] bf16, loss [B] fp32 or None, saved)."""
+    # forward, decode and score_continuations are compositions of self_attn_fwd .. mlp_fwd above and the pieces below; they differ in what
+    # a self-attention sees (`attend`), in where the cross-attention K/V come from (`cross`) and in what they keep for a backward.
+    def _embed(self, ids, drop=None, pos_base=None):
         d, P = self.d, self.P
-        B, T = input_ids.shape
-        S = enc.shape[1]
-        H = d.hidden_size
         e = 'roberta.embeddings.'
-        input_ids = input_ids.contiguous()
-        key_mask = None
-        if attention_mask is not None:
-            key_mask = (attention_mask != 0).to(torch.uint8).contiguous()
-        enc2 = enc.reshape(B * S, enc.shape[2])
-        sv = [] if save else None
-        dr_e = self.drop(9000, d.hidden_dropout_prob, seed)
-        h, xhat, erstd, hf = ops.embed_fwd(input_ids, P.f(e + 'word_embeddings.weight'), P.f(e + 'position_embeddings.weight'),
-                                       P.f(e + 'token_type_embeddings.weight'), P.f(e + 'LayerNorm.weight'), P.f(e + 'LayerNorm.bias'),
-                                       d.layer_norm_eps, d.pad_token_id, dr_e, want_f32=True)
-        # the K/V projections of all cross-attention layers depend on `enc` only: issue them up front on a branch stream
-        # (12 x [B*S, 2H] GEMMs that overlap the latency-bound decoder chain); each layer waits on its own event.
-        kvs, kv_evs = [None] * len(self.layers), [None] * len(self.layers)
-        branch = self.kv_prefetch and isinstance(ops.POOL, ops.BranchPool)
+        return ops.embed_fwd(ids.contiguous(), P.f(e + 'word_embeddings.weight'), P.f(e + 'position_embeddings.weight'),
+                             P.f(e + 'token_type_embeddings.weight'), P.f(e + 'LayerNorm.weight'), P.f(e + 'LayerNorm.bias'),
+                             d.layer_norm_eps, d.pad_token_id, drop, want_f32=True, pos_base=pos_base)
+
+    @staticmethod
+    def _key_mask(att):
+        return None if att is None else (att != 0).to(torch.uint8).contiguous()
+
+    def _project_kv(self, enc2, branch):
+        """The K/V projections of all cross-attention layers depend on `enc` only.  Returns (kvs, kv_evs), one entry per layer: the layer's
+        [B*S, 2H] K | V (None: the layer projects its own) and the event its cross-attention waits on (None: same stream).
+        branch: issue them up front on a branch stream (12 x [B*S, 2H] GEMMs that overlap the latency-bound decoder chain)."""
+        H, nl = self.d.hidden_size, len(self.layers)
+        kvs, kv_evs = [None] * nl, [None] * nl
         if self.kv_all is not None:                      # ONE [B*S, 2H*layers] GEMM; every layer reads its column slice
-            def all_kv():
-                return self.kv_all.fwd(enc2)
             if branch:
                 with ops.POOL.branch(0):
-                    kva = all_kv()
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream())
+                    kva = self.kv_all.fwd(enc2)
+                    kv_evs[0] = torch.cuda.Event()
+                    kv_evs[0].record(torch.cuda.current_stream())
                 ops.POOL.used.clear()                    # joined through the event the first cross-attention waits on
-                kv_evs[0] = ev
             else:
-                kva = all_kv()
-            kvs = [kva[:, 2 * H * i:2 * H * (i + 1)] for i in range(len(self.layers))]
+                kva = self.kv_all.fwd(enc2)
+            kvs = [kva[:, 2 * H * i:2 * H * (i + 1)] for i in range(nl)]
         elif branch:
             with ops.POOL.branch(0):
                 for i, L in enumerate(self.layers):
                     kvs[i] = L['ca']['kv'].fwd(enc2)
                     kv_evs[i] = torch.cuda.Event()
                     kv_evs[i].record(torch.cuda.current_stream())
-            ops.POOL.used.clear()        # joined through the per-layer events below (the last one covers the whole branch)
+            ops.POOL.used.clear()        # joined through the per-layer events (the last one covers the whole branch)
+        return kvs, kv_evs
+
+    def _layers(self, h, hf, attend, cross, seed, sv):
+        """12 x [self-attn, cross-attn, Adaptor, MLP] + output_layer; cross(i, blk, h, hf) is layer i's cross-attention"""
         for i, L in enumerate(self.layers):
-            h, hf = self.self_attn_fwd(L['sa'], L['idx'], h, hf, B, T, key_mask, seed, sv)
-            h, hf = self.cross_attn_fwd(L['ca'], L['idx'], h, hf, enc2, B, T, S, seed, sv, kvs[i], kv_evs[i])
+            h, hf = self.self_attn_fwd(L['sa'], L['idx'], h, hf, attend, seed, sv)
+            h, hf = cross(i, L['ca'], h, hf)
             h, hf = self.adaptor_fwd(L['ad'], h, hf, sv)
             h, hf = self.mlp_fwd(L['mlp'], L['idx'], h, hf, seed, sv)
         F_ = self.final
-        h, hf = self.self_attn_fwd(F_['sa'], F_['idx'], h, hf, B, T, key_mask, seed, sv)
-        h, hf = self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, seed, sv)
-        t0pre = torch.empty_like(h)
+        h, hf = self.self_attn_fwd(F_['sa'], F_['idx'], h, hf, attend, seed, sv)
+        return self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, seed, sv)
+
+    def _lm_head(self, h, keep):
+        """RobertaLMHead: dense (GELU) -> LayerNorm -> tied decoder weight.  Returns (logits [rows, Vpad] bf16, what the backward needs of it
+        when `keep`: the pre-activation and the LayerNorm statistics are only written then)."""
+        d, P = self.d, self.P
+        t0pre = torch.empty_like(h) if keep else None
         t0 = self.head_dense.fwd(h, act=ACT_GELU, pre_out=t0pre)
-        t1, hm, hr = self.head_ln.fwd(t0)
-        V = d.vocab_size
-        logits = torch.empty(B * T, self.Vpad, dtype=BF16, device=h.device)
-        ops.gemm(t1, P.w(e + 'word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=V)      # tied decoder weight
+        t1, hm, hr = self.head_ln.fwd(t0, save_stats=keep)
+        logits = torch.empty(h.shape[0], self.Vpad, dtype=BF16, device=h.device)
+        ops.gemm(t1, P.w('roberta.embeddings.word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=d.vocab_size)
+        return logits, (dict(t0pre=t0pre, t0=t0, t1=t1, hm=hm, hr=hr) if keep else None)
+
+    def forward(self, input_ids, attention_mask, enc, labels, seed, save, want_logits=True):
+        """enc: [B, S, Hv] bf16 contiguous. seed: int64[1] device tensor or None (no dropout = eval mode).
+        Returns (logits_buf [B*T, Vpad] bf16, loss [B] fp32 or None, saved)."""
+        d = self.d
+        B, T = input_ids.shape
+        S = enc.shape[1]
+        H, nh = d.hidden_size, d.num_attention_heads
+        input_ids = input_ids.contiguous()
+        key_mask = self._key_mask(attention_mask)
+        enc2 = enc.reshape(B * S, enc.shape[2])
+        sv = [] if save else None
+        dr_e = self.drop(9000, d.hidden_dropout_prob, seed)
+        h, xhat, erstd, hf = self._embed(input_ids, dr_e)
+        kvs, kv_evs = self._project_kv(enc2, self.kv_prefetch and isinstance(ops.POOL, ops.BranchPool))
+
+        def attend(li, qkv):                             # causal self-attention on the packed qkv
+            st = (T * 3 * H, 3 * H)
+            dr_a = self.drop(li * 16 + 1, d.attention_probs_dropout_prob, seed)
+            return ops.attention_fwd(qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], B, nh, T, T, H // nh, q_strides=st, k_strides=st, v_strides=st,
+                                     key_mask=key_mask, causal=True, drop=dr_a) + (dr_a,)
+
+        def cross(i, blk, h, hf):
+            return self.cross_attn_fwd(blk, i, h, hf, enc2, B, T, S, seed, sv, kvs[i], kv_evs[i])
+        h, hf = self._layers(h, hf, attend, cross, seed, sv)
+        logits, head = self._lm_head(h, True)
         loss = row_lse = None
         if labels is not None:
             labels = labels.contiguous()
-            loss, row_lse = ops.ce_fwd(logits, labels, B, T, V, d.label_smoothing)
+            loss, row_lse = ops.ce_fwd(logits, labels, B, T, d.vocab_size, d.label_smoothing)
         saved = None
         if save:
             saved = dict(blocks=sv, B=B, T=T, S=S, ids=input_ids, key_mask=key_mask, enc=enc2, xhat=xhat, erstd=erstd, dr_e=dr_e, hL=h,
-                         t0pre=t0pre, t0=t0, t1=t1, hm=hm, hr=hr, logits=logits, labels=labels, row_lse=row_lse)
+                         logits=logits, labels=labels, row_lse=row_lse, **head)
         return logits, loss, saved
 
     # ---------------------------------------------------------------------------------------- KV-cached inference
@@ -273,10 +300,8 @@ class DecoderProgram:
         Bb, S, Hv = enc.shape
         H = d.hidden_size
         enc2 = enc.reshape(Bb * S, Hv)
-        if self.kv_all is not None:
-            kva = self.kv_all.fwd(enc2)
-            kvs = [kva[:, 2 * H * i:2 * H * (i + 1)] for i in range(len(self.layers))]
-        else:
+        kvs, _ = self._project_kv(enc2, False)
+        if self.kv_all is None:                          # per-layer linears: projected here, not inside every step's cross-attention
             kvs = [L['ca']['kv'].fwd(enc2) for L in self.layers]
         nl = len(self.layers) + 1
         cache = [torch.zeros(nl, Bb, Tmax, 2 * H, dtype=BF16, device=enc.device) for _ in range(2)]     # ping-pong for beam reordering
@@ -290,60 +315,41 @@ class DecoderProgram:
         ops.gather_rows(src.view(nl * Bb, Tmax * W2), idx, dst.view(nl * Bb, Tmax * W2), cols=st['filled'] * W2)
         st['cur'] ^= 1
 
-    def _self_attn_cached(self, blk, li, slot, h, hf, st, t0, T, key_mask):
-        d = self.d
-        H, nh = d.hidden_size, d.num_attention_heads
-        dh = H // nh
-        Bb, Tmax = st['Bb'], st['Tmax']
-        Sq = T - t0
-        qkv = blk['qkv'].fwd(h)                                                  # [Bb*Sq, 3H]
-        cache = st['cache'][st['cur']][slot]                                     # [Bb, Tmax, 2H]
-        # K | V rows of the new positions -> cache[:, t0:T]
-        ops.copy_rows(qkv[:, H:], cache.view(Bb * Tmax, 2 * H), Bb * Sq, 2 * H, dst_map=ops.RowMap(Sq, Tmax, t0), src_ld=3 * H, dst_ld=2 * H)
-        cs = (Tmax * 2 * H, 2 * H)
-        o, _ = ops.attention_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], Bb, nh, Sq, T, dh, q_strides=(Sq * 3 * H, 3 * H), k_strides=cs,
-                                 v_strides=cs, key_mask=key_mask, causal=Sq > 1)
-        s = blk['out'].fwd(o, residual=hf, out_f32=True)
-        y, yf, _, _ = self.post_ln(blk['ln'], s)
-        return y, yf
+    def _cached_cross(self, st, B, Tq):
+        """cross-attention of Tq query tokens per image row against the K/V `decode_begin` projected"""
+        def cross(i, blk, h, hf):
+            return self.cross_attn_fwd(blk, i, h, hf, None, B, Tq, st['S'], None, None, st['kvs'][i])
+        return cross
 
     def decode(self, st, input_ids, attention_mask, t0):
         """runs positions t0 .. T-1 of input_ids [Bb, T] (t0 == 0: prefill, causal; otherwise exactly the last position) against
         the caches and returns the logits of the LAST position, fp32 view [Bb, V] of a bf16 buffer."""
-        d, P = self.d, self.P
+        d = self.d
         Bb, T = input_ids.shape
         assert Bb == st['Bb'] and T <= st['Tmax'] and (t0 == 0 or t0 == T - 1), 'decode: prefill (t0=0) or single-token steps only'
-        H, S = d.hidden_size, st['S']
-        e = 'roberta.embeddings.'
+        H, nh, Tmax = d.hidden_size, d.num_attention_heads, st['Tmax']
         Sq = T - t0
-        key_mask = None
-        if attention_mask is not None:
-            key_mask = (attention_mask != 0).to(torch.uint8).contiguous()
-        h_all, _, _, hf_all = ops.embed_fwd(input_ids.contiguous(), P.f(e + 'word_embeddings.weight'), P.f(e + 'position_embeddings.weight'),
-                                            P.f(e + 'token_type_embeddings.weight'), P.f(e + 'LayerNorm.weight'), P.f(e + 'LayerNorm.bias'),
-                                            d.layer_norm_eps, d.pad_token_id, None, want_f32=True)
+        key_mask = self._key_mask(attention_mask)
+        h_all, _, _, hf_all = self._embed(input_ids)
         if t0 == 0:
             h, hf = h_all, hf_all
         else:                                                                     # the new position of every row
             h = h_all.view(Bb, T, H)[:, t0:].reshape(Bb * Sq, H).contiguous()
             hf = hf_all.view(Bb, T, H)[:, t0:].reshape(Bb * Sq, H).contiguous()
-        for i, L in enumerate(self.layers):
-            h, hf = self._self_attn_cached(L['sa'], L['idx'], i, h, hf, st, t0, T, key_mask)
-            h, hf = self.cross_attn_fwd(L['ca'], L['idx'], h, hf, None, Bb, Sq, S, None, None, st['kvs'][i])
-            h, hf = self.adaptor_fwd(L['ad'], h, hf, None)
-            h, hf = self.mlp_fwd(L['mlp'], L['idx'], h, hf, None, None)
-        F_ = self.final
-        h, hf = self._self_attn_cached(F_['sa'], F_['idx'], len(self.layers), h, hf, st, t0, T, key_mask)
-        h, hf = self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, None, None)
+
+        def attend(li, qkv):                                                      # qkv [Bb*Sq, 3H]
+            cache = st['cache'][st['cur']][li]                                    # [Bb, Tmax, 2H]
+            # K | V rows of the new positions -> cache[:, t0:T]
+            ops.copy_rows(qkv[:, H:], cache.view(Bb * Tmax, 2 * H), Bb * Sq, 2 * H, dst_map=ops.RowMap(Sq, Tmax, t0), src_ld=3 * H, dst_ld=2 * H)
+            cs = (Tmax * 2 * H, 2 * H)
+            return ops.attention_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], Bb, nh, Sq, T, H // nh, q_strides=(Sq * 3 * H, 3 * H),
+                                     k_strides=cs, v_strides=cs, key_mask=key_mask, causal=Sq > 1) + (None,)
+        h, hf = self._layers(h, hf, attend, self._cached_cross(st, Bb, Sq), None, None)
         st['filled'] = max(st['filled'], T)
         st['key_mask'] = key_mask                                                # (the prefix key mask of score_continuations)
         last = h if Sq == 1 else h.view(Bb, Sq, H)[:, -1].contiguous()           # LM head on the last position only
-        t0_ = self.head_dense.fwd(last, act=ACT_GELU)
-        t1, _, _ = self.head_ln.fwd(t0_, save_stats=False)
-        V = d.vocab_size
-        logits = torch.empty(Bb, self.Vpad, dtype=BF16, device=h.device)
-        ops.gemm(t1, P.w(e + 'word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=V)
-        return logits[:, :V]
+        logits, _ = self._lm_head(last, False)
+        return logits[:, :d.vocab_size]
 
     # ---------------------------------------------------------------------------------------- shared-prefix scoring
     # inference='rank' (prismer_caption.py:59-112, prismer_vqa.py:64-113) runs [prompt || candidate] for k candidates of every image.  Causal
@@ -351,50 +357,30 @@ class DecoderProgram:
     # self-attention K/V cache, cross-attention K/V projected once per image) and only the continuations run per candidate: their
     # self-attention reads the cached prefix K/V of their image (ph_attention_prefix_fwd, nothing copied k times), their cross-attention
     # reads the image's K/V with the k*Tc continuation tokens of the image as one query block.
-    def _self_attn_shared(self, blk, slot, h, hf, st, R, Tc, Tp, group, cont_mask):
-        d = self.d
-        H, nh = d.hidden_size, d.num_attention_heads
-        dh = H // nh
-        Tmax = st['Tmax']
-        qkv = blk['qkv'].fwd(h)                                                  # [R*Tc, 3H]
-        cache = st['cache'][st['cur']][slot]                                     # [images, Tmax, 2H]: prefix K | V
-        pm = st.get('key_mask')
-        cs, qs = (Tmax * 2 * H, 2 * H), (Tc * 3 * H, 3 * H)
-        o = ops.attention_prefix_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], qkv[:, H:2 * H], qkv[:, 2 * H:], R, nh, Tc, Tp, group, dh,
-                                     q_strides=qs, pk_strides=cs, pv_strides=cs, ck_strides=qs, cv_strides=qs,
-                                     prefix_mask=pm, pm_stride=0 if pm is None else pm.stride(0), cont_mask=cont_mask, cm_stride=Tc)
-        s = blk['out'].fwd(o, residual=hf, out_f32=True)
-        y, yf, _, _ = self.post_ln(blk['ln'], s)
-        return y, yf
-
     def score_continuations(self, st, cont_ids, cont_att, labels, pos_base, Tp, group):
         """Per-row loss [R] fp32 (the summed, shifted, label-smoothed CE of `forward`) of R = images * group continuation rows
         cont_ids [R, Tc] (row r continues prefix row r // group of the state `decode_begin` + the prefill `decode` produced) under
         cont_att [R, Tc] and labels [R, Tc] (-100 = not scored).  The continuation attends to the prefix positions 0 .. Tp-1 (prefix key
         mask of the prefill) and, causally, to itself; real tokens take positions pad + pos_base[r] + cumsum(cont_ids != pad)."""
-        d, P = self.d, self.P
+        d = self.d
         R, Tc = cont_ids.shape
-        B, S = st['Bb'], st['S']
+        B, Tmax = st['Bb'], st['Tmax']
         assert R == B * group and 0 <= Tp <= st['filled'], 'score_continuations: group rows per prefix row, Tp within the prefill'
-        e = 'roberta.embeddings.'
-        cont_mask = (cont_att != 0).to(torch.uint8).contiguous()
-        h, _, _, hf = ops.embed_fwd(cont_ids.contiguous(), P.f(e + 'word_embeddings.weight'), P.f(e + 'position_embeddings.weight'),
-                                    P.f(e + 'token_type_embeddings.weight'), P.f(e + 'LayerNorm.weight'), P.f(e + 'LayerNorm.bias'),
-                                    d.layer_norm_eps, d.pad_token_id, None, want_f32=True, pos_base=pos_base.to(torch.int32).contiguous())
-        for i, L in enumerate(self.layers):
-            h, hf = self._self_attn_shared(L['sa'], i, h, hf, st, R, Tc, Tp, group, cont_mask)
-            h, hf = self.cross_attn_fwd(L['ca'], L['idx'], h, hf, None, B, group * Tc, S, None, None, st['kvs'][i])
-            h, hf = self.adaptor_fwd(L['ad'], h, hf, None)
-            h, hf = self.mlp_fwd(L['mlp'], L['idx'], h, hf, None, None)
-        F_ = self.final
-        h, hf = self._self_attn_shared(F_['sa'], len(self.layers), h, hf, st, R, Tc, Tp, group, cont_mask)
-        h, hf = self.mlp_fwd(F_['mlp'], F_['idx'], h, hf, None, None)
-        t0 = self.head_dense.fwd(h, act=ACT_GELU)
-        t1, _, _ = self.head_ln.fwd(t0, save_stats=False)
-        V = d.vocab_size
-        logits = torch.empty(R * Tc, self.Vpad, dtype=BF16, device=h.device)
-        ops.gemm(t1, P.w(e + 'word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=V)
-        loss, _ = ops.ce_fwd(logits, labels.contiguous(), R, Tc, V, d.label_smoothing)
+        H, nh = d.hidden_size, d.num_attention_heads
+        cont_mask = self._key_mask(cont_att)
+        h, _, _, hf = self._embed(cont_ids, pos_base=pos_base.to(torch.int32).contiguous())
+        pm = st.get('key_mask')
+
+        def attend(li, qkv):                                                      # qkv [R*Tc, 3H]
+            cache = st['cache'][st['cur']][li]                                    # [images, Tmax, 2H]: prefix K | V
+            cs, qs = (Tmax * 2 * H, 2 * H), (Tc * 3 * H, 3 * H)
+            o = ops.attention_prefix_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], qkv[:, H:2 * H], qkv[:, 2 * H:], R, nh, Tc, Tp, group,
+                                         H // nh, q_strides=qs, pk_strides=cs, pv_strides=cs, ck_strides=qs, cv_strides=qs,
+                                         prefix_mask=pm, pm_stride=0 if pm is None else pm.stride(0), cont_mask=cont_mask, cm_stride=Tc)
+            return o, None, None
+        h, hf = self._layers(h, hf, attend, self._cached_cross(st, B, group * Tc), None, None)
+        logits, _ = self._lm_head(h, False)
+        loss, _ = ops.ce_fwd(logits, labels.contiguous(), R, Tc, d.vocab_size, d.label_smoothing)
         return loss
 
     def backward(self, sv, dloss):
