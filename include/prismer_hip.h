@@ -32,7 +32,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* ABI revision: bumped whenever an argument struct or a signature changes (101: ph_conv_gather window fields, ph_gemm_args row map +
  * defer_reduce; 102: round 4; 103: round 5 -- ph_ce_fwd takes a row_loss scratch, no memset nodes anywhere; 104: round 6 -- ph_dense_minmax_partial,
- * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
+ * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
 #define PH_VERSION 105
 
 enum { PH_OK = 0, PH_ERR_BAD_ARG = -1, PH_ERR_UNSUPPORTED = -2, PH_ERR_LAUNCH = -3 };
@@ -352,6 +352,53 @@ int ph_ce_bwd(void* logits, int ld, const int64_t* labels, int B, int T, int V, 
 int ph_softmax_gather_bf16(const void* logits, int64_t ld, int rows, int V, const int64_t* ids, int n, float* out, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Beam-search step (inference='generate': model/prismer_caption.py:45-50, model/prismer_vqa.py:52-58 call transformers' generate with
+ * num_beams = 3; transformers 4.26.1 BeamSearchScorer.process, BeamHypotheses.add / is_done, MinLengthLogitsProcessor).
+ * ph_beam_topk: for each of B images the best 2*nb candidates (beam, token) of
+ *     score = beam_scores[row] + (logits[row][tok] - lse(row)),   row = image * nb_in + beam
+ * in fp32, in that order of operations; lse(row) = max + log(sum exp(x - max)) over the V columns from one sweep, ONE value per row, so
+ * two columns of a row that hold the same bf16 value get bit-equal scores.  nb_in = nb: one logit row per beam; nb_in = 1: one row per
+ * image (the first step after a per-image prefill; `beam` is then 0).  ban_eos != 0: column eos_token_id is no candidate (it still
+ * counts in lse: MinLengthLogitsProcessor works on the log-probabilities).
+ * THE ORDER IS DEFINED, best first: score descending, then flat index beam * V + tok ascending.  (Where fp32 rounding gives two
+ * DIFFERENT logits of one row the same score -- only when |beam score| is many orders above the logits -- the higher logit goes first.)
+ * Each logit is read once: rows are split over blocks that leave (max, sum, 2*nb best) records in `workspace`
+ * (ph_query_workspace(PH_WS_BEAM_TOPK)), a second small kernel merges them per image.  No atomics.
+ * Limits: 1 <= nb <= 8, 2*nb + 1 <= V <= 524288, ld % 8 == 0, ld >= V, logits 16-byte aligned; else PH_ERR_BAD_ARG before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* logits; int64_t ld; /* bf16 [B*nb_in][ld], V valid columns */
+  int V, B, nb, nb_in;
+  const float* beam_scores;       /* fp32 [B*nb_in] */
+  int eos_token_id, ban_eos;
+  void* workspace; int64_t workspace_bytes;
+  float* top_score;               /* fp32 [B][2*nb] */
+  int32_t* top_beam; int32_t* top_tok;   /* int32 [B][2*nb] */
+} ph_beam_topk_args;
+int ph_beam_topk(const ph_beam_topk_args* args, hipStream_t stream);
+/* ph_beam_advance: the bookkeeping of one step for all B items in one launch, from ph_beam_topk's output and the search state.  Per
+ * item that is not done: the 2*nb candidates are visited in order until nb continuing beams are collected; an EOS candidate of rank < nb
+ * becomes a hypothesis (score top_score / len_div, tokens = row of its beam with EOS at `cur`, length cur + 1; kept while fewer than nb
+ * are held, else it replaces the worst one if strictly better), an EOS of rank >= nb is dropped; then
+ * done |= n_hyp >= nb && min(hyp_score) >= top_score[0] / len_div.  A done item gets padding beams (score 0, pad token, its first row).
+ * ids_out row image*nb + k = ids_in row image*nb + beam_k with token_k at `cur` (ids_in / ids_out: the two halves of a ping-pong,
+ * always nb rows per image); beam_scores[image*nb + k] = score_k;
+ * rows_out[l * B*nb + image*nb + k] = l * B*nb + image*nb_in + beam_k for l < rows_rep: the source row of every beam among the rows
+ * the logits came from (rows_rep > 1: the gather index of a [rows_rep][B*nb] stack of caches in one piece).
+ * len_div = cur ** length_penalty, computed by the host.  State: hyp_score fp32 [B][nb] (-inf = empty), hyp_tok int64 [B][nb][Tmax],
+ * hyp_len int32 [B][nb], n_hyp int32 [B], done int32 [B]. */
+typedef struct {
+  const float* top_score; const int32_t* top_beam; const int32_t* top_tok;
+  const int64_t* ids_in; int64_t* ids_out;
+  float* beam_scores;
+  float* hyp_score; int64_t* hyp_tok; int32_t* hyp_len; int32_t* n_hyp; int32_t* done;
+  int32_t* rows_out;
+  int B, nb, nb_in, Tmax, cur, eos_token_id, pad_token_id, rows_rep;
+  float len_div;
+} ph_beam_advance_args;
+int ph_beam_advance(const ph_beam_advance_args* args, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Optimizer and small utilities.
  * ---------------------------------------------------------------------------------------------- */
 /* torch.optim.AdamW step (train_caption.py:111-112,133) over a flat fp32 range; also refreshes the bf16 shadow.
@@ -416,8 +463,11 @@ int ph_gemm_dispatch_counts(int64_t* out, int n, int reset);
  *   PH_WS_GEMM_SPLITK     dims = {M, N, K}: ph_gemm_args.workspace (split-K partial tiles, up to 256 splits of [M][N rounded to 4] fp32)
  *   PH_WS_LAYERNORM_BWD   dims = {M, D}:    ph_layernorm_bwd_args.partial_ws ([ph_layernorm_bwd_blocks(M)][2][D] fp32)
  *   PH_WS_ATTENTION_BWD   dims = {B, H, Sq}: ph_attn_bwd_args.delta ([B*H*Sq] fp32)
- *   PH_WS_CONV_COLSTATS   dims = {N}:       ph_gemm_args.col_stats ([PH_COLSTAT_SLABS][2][N] fp64, zeroed by the caller) */
-enum { PH_WS_GEMM_SPLITK = 0, PH_WS_LAYERNORM_BWD = 1, PH_WS_ATTENTION_BWD = 2, PH_WS_CONV_COLSTATS = 3 };
+ *   PH_WS_CONV_COLSTATS   dims = {N}:       ph_gemm_args.col_stats ([PH_COLSTAT_SLABS][2][N] fp64, zeroed by the caller)
+ *   PH_WS_BEAM_TOPK       dims = {B, nb, V}: ph_beam_topk_args.workspace, enough for nb_in = 1 and nb_in = nb:
+ *                                            max(B * split(B, V), B*nb * split(B*nb, V)) records of 34 words, with
+ *                                            split(rows, V) = max(ceil(V / 8192), min(16, ceil(512 / rows), ceil(V / 1024))) */
+enum { PH_WS_GEMM_SPLITK = 0, PH_WS_LAYERNORM_BWD = 1, PH_WS_ATTENTION_BWD = 2, PH_WS_CONV_COLSTATS = 3, PH_WS_BEAM_TOPK = 4 };
 int64_t ph_query_workspace(int op, const int64_t* dims, int ndims);
 /* per-step host scalars written by a kernel whose ARGUMENTS carry them (no copy engine, no pinned staging): dst0[0..n0) and dst1[0..n1)
  * (32-bit words, device memory; dst1 may be NULL with n1 = 0) <- host_words[0..n0+n1), read before the call returns.  Replaces the two

@@ -133,6 +133,24 @@ class EmbedBwdArgs(C.Structure):
                 ('dtype', c_void_p), ('dgamma', c_void_p), ('dbeta', c_void_p)]
 
 
+class BeamTopkArgs(C.Structure):
+    _fields_ = [('logits', c_void_p), ('ld', c_i64), ('V', c_int), ('B', c_int), ('nb', c_int), ('nb_in', c_int),
+                ('beam_scores', c_void_p), ('eos_token_id', c_int), ('ban_eos', c_int),
+                ('workspace', c_void_p), ('workspace_bytes', c_i64),
+                ('top_score', c_void_p), ('top_beam', c_void_p), ('top_tok', c_void_p)]
+
+
+class BeamAdvanceArgs(C.Structure):
+    _fields_ = [('top_score', c_void_p), ('top_beam', c_void_p), ('top_tok', c_void_p),
+                ('ids_in', c_void_p), ('ids_out', c_void_p), ('beam_scores', c_void_p),
+                ('hyp_score', c_void_p), ('hyp_tok', c_void_p), ('hyp_len', c_void_p), ('n_hyp', c_void_p), ('done', c_void_p),
+                ('rows_out', c_void_p),
+                ('B', c_int), ('nb', c_int), ('nb_in', c_int), ('Tmax', c_int), ('cur', c_int), ('eos_token_id', c_int),
+                ('pad_token_id', c_int), ('rows_rep', c_int), ('len_div', c_float)]
+
+
+WS_BEAM_TOPK = 4         # PH_WS_BEAM_TOPK
+
 _SIGS = {
     'ph_version': (c_int, []),
     'ph_last_error': (C.c_char_p, []),
@@ -166,6 +184,8 @@ _SIGS = {
     'ph_embed_fwd_offset': (c_int, [C.POINTER(EmbedFwdArgs), c_void_p, c_void_p]),
     'ph_embed_bwd': (c_int, [C.POINTER(EmbedBwdArgs), c_void_p]),
     'ph_softmax_gather_bf16': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    'ph_beam_topk': (c_int, [C.POINTER(BeamTopkArgs), c_void_p]),
+    'ph_beam_advance': (c_int, [C.POINTER(BeamAdvanceArgs), c_void_p]),
     'ph_ce_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ph_ce_bwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'ph_adamw': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,

@@ -21,6 +21,7 @@ int ph_fail(int code, const char* fmt, ...) {
 extern "C" int ph_version(void) { return PH_VERSION; }
 
 extern "C" int ph_layernorm_bwd_blocks(int M);
+int64_t beam_topk_workspace_bytes(int64_t B, int64_t nb, int64_t V);     // beam.hip
 extern "C" int64_t ph_query_workspace(int op, const int64_t* dims, int ndims) {
   if (!dims) return -1;
   switch (op) {
@@ -38,6 +39,9 @@ extern "C" int64_t ph_query_workspace(int op, const int64_t* dims, int ndims) {
     case PH_WS_CONV_COLSTATS:
       if (ndims != 1 || dims[0] <= 0) return -1;
       return (int64_t)PH_COLSTAT_SLABS * 2 * dims[0] * 8;
+    case PH_WS_BEAM_TOPK:
+      if (ndims != 3) return -1;
+      return beam_topk_workspace_bytes(dims[0], dims[1], dims[2]);
     default:
       return -1;
   }

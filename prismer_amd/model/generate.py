@@ -8,10 +8,18 @@ the FULL prefix every step (prepare_inputs_for_generation, roberta.py:401-406, p
 Here:
   * the decoder runs KV-cached (DecoderProgram.decode_begin / decode / decode_reorder): cross-attention K/V projected once,
     self-attention K/V cached per layer and re-ordered with the beams on the device;
-  * the beam bookkeeping is vectorised over the batch with tensor ops on the device the logits live on -- no `.tolist()` /
-    host round trip per step (the only synchronisation is the final read-out);
-  * `beam_search_from_logits` is the algorithm alone (any callable that maps the current ids to next-token logits): it runs on
-    CPU tensors too, which is how tests/test_generate_cpu.py checks it against the loop-form oracle (oracle/beam_oracle.py).
+  * with `share_image` the `num_beams` hypotheses of an image share the image's cross-attention K/V (projected for B images, not
+    B * num_beams) and the prompt runs once per image: at the first step every beam but the first starts at -1e9 anyway;
+  * the beam step runs on the device: `beam_search_device` is `step_fn -> ops.beam_topk -> ops.beam_advance -> reorder_fn`, two library
+    calls on device-resident state, no stock torch reduction / sort / top-k / boolean-mask indexing and no host read inside the loop
+    but the "all items done?" check every fourth step;
+  * `beam_search_from_logits` is the algorithm alone, as tensor ops (any callable that maps the current ids to next-token logits): the
+    SPECIFICATION of the device step.  It runs on CPU tensors, which is how tests/test_generate_cpu.py checks it against the loop-form
+    oracle (oracle/beam_oracle.py).  On a GPU its boolean-mask indexing synchronises with the device several times per step.
+
+Ties.  `torch.topk` leaves the order of equal candidates undefined, and with bf16 logits exact ties among a row's leaders are common.
+The library's rule (ph_beam_topk) is: score descending, then flat index beam * V + token ascending -- `stable_topk` below; pass it
+as `topk_fn` to run the specification under that rule.
 
 Semantics kept from transformers 4.26.1 (num_return_sequences = 1, early_stopping = False, do_sample = False):
   - scores of the first step come from beam 0 only (the other beams start at -1e9);
@@ -28,12 +36,23 @@ import torch
 NEG = -1e9
 
 
+def stable_topk(cand, k):
+    """(values, indices) of the k best entries of every row of cand [B, N], best first, equal values in ascending index order: the
+    tie rule of ph_beam_topk as tensor ops"""
+    s, i = torch.sort(cand, dim=1, descending=True, stable=True)
+    return s[:, :k], i[:, :k]
+
+
 @torch.no_grad()
 def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
-                            length_penalty=1.0, reorder_fn=None):
+                            length_penalty=1.0, reorder_fn=None, topk_fn=None):
     """step_fn(ids [B*nb, T]) -> next-token logits [B*nb, V] (any float dtype) for the LAST position of every row.
     reorder_fn(rows int64 [B*nb]) is called after each step with the source row of every continuing beam (cache re-ordering).
-    Returns a list of B 1-D LongTensors (prompt + generated tokens, EOS included when the hypothesis ended with one)."""
+    topk_fn(cand [B, nb*V], k) -> (values, indices), best first; None = `cand.topk(k, dim=1)`, whose order among equal candidates is
+    torch's; `stable_topk` is the library's rule.
+    Returns a list of B 1-D LongTensors (prompt + generated tokens, EOS included when the hypothesis ended with one).
+    All tensor ops, on the device of input_ids -- but not free of host round trips there: every boolean-mask index below is a
+    `nonzero`, which waits for the device."""
     B, T0 = input_ids.shape
     dev = input_ids.device
     nb = num_beams
@@ -70,7 +89,7 @@ def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_
         if cur < min_length:
             logp[:, eos_token_id] = -float('inf')
         cand = (beam_scores.view(-1, 1) + logp).view(B, nb * V)
-        top_s, top_i = cand.topk(2 * nb, dim=1)                          # sorted, best first
+        top_s, top_i = cand.topk(2 * nb, dim=1) if topk_fn is None else topk_fn(cand, 2 * nb)      # sorted, best first
         top_beam, top_tok = top_i // V, top_i % V
         n_next = torch.zeros(B, dtype=torch.long, device=dev)
         nxt_score = torch.zeros(B, nb, device=dev)
@@ -117,29 +136,129 @@ def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_
 
 
 @torch.no_grad()
+def beam_search_device(step_fn, input_ids, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
+                       length_penalty=1.0, reorder_fn=None, rows_rep=1):
+    """beam_search_from_logits with the beam step in the library (ops.beam_topk, ops.beam_advance) and the search state in device
+    buffers allocated once: same arguments, same return value, ties by the library's rule.
+    step_fn(ids [B*nb, T]) -> bf16 logits on the GPU, [B*nb, V], or [B, V] when one row stands for all beams of its item (the first
+    step after a per-image prefill).  reorder_fn(rows int32 [rows_rep * B*nb]) gets, for l < rows_rep, l * B*nb + the source row of
+    every continuing beam AMONG THE ROWS step_fn RETURNED (rows_rep > 1: the gather index of a stack of caches)."""
+    from .. import ops
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    nb, Tmax = num_beams, max_length
+    i32 = torch.int32
+    ids = [torch.full((B * nb, Tmax), pad_token_id, dtype=torch.long, device=dev) for _ in range(2)]      # ping-pong
+    ids[0][:, :T0] = input_ids.repeat_interleave(nb, dim=0)
+    which = 0
+    beam_scores = torch.zeros(B, nb, device=dev)
+    beam_scores[:, 1:] = NEG
+    first_scores = torch.zeros(B, device=dev)                             # one row per item: that row is beam 0
+    hyp_score = torch.full((B, nb), -float('inf'), device=dev)
+    hyp_tok = torch.full((B, nb, Tmax), pad_token_id, dtype=torch.long, device=dev)
+    hyp_len = torch.zeros(B, nb, dtype=i32, device=dev)
+    n_hyp = torch.zeros(B, dtype=i32, device=dev)
+    done = torch.zeros(B, dtype=i32, device=dev)
+    rows = torch.empty(rows_rep * B * nb, dtype=i32, device=dev)
+    top = (torch.empty(B, 2 * nb, device=dev), torch.empty(B, 2 * nb, dtype=i32, device=dev), torch.empty(B, 2 * nb, dtype=i32, device=dev))
+    ws = None
+    cur = T_start = T0
+    while cur < Tmax:
+        logits = step_fn(ids[which][:, :cur])
+        if ws is None:
+            ws = ops.beam_topk_workspace(B, nb, logits.shape[1], dev)
+        nb_in = logits.shape[0] // B
+        ops.beam_topk(logits, beam_scores if nb_in == nb else first_scores, B, nb, eos_token_id, cur < min_length, workspace=ws, out=top)
+        ops.beam_advance(top, ids[which], ids[which ^ 1], beam_scores, hyp_score, hyp_tok, hyp_len, n_hyp, done, rows, nb_in, cur,
+                         eos_token_id, pad_token_id, float(cur) ** length_penalty)
+        which ^= 1
+        if reorder_fn is not None:
+            reorder_fn(rows)
+        cur += 1
+        if (cur - T_start) % 4 == 0 and bool(done.cpu().all()):           # the one host read: B flags, every fourth step
+            break
+    # finalize, once per call, on the host (the state is B * nb token rows): running beams of unfinished items become hypotheses
+    # (score / cur_len ** lp, BeamHypotheses.add as above), the best hypothesis wins
+    cur_ids = ids[which].view(B, nb, Tmax).cpu()
+    beam_scores, hyp_score, hyp_tok, hyp_len, n_hyp = (t.cpu() for t in (beam_scores.view(B, nb), hyp_score, hyp_tok, hyp_len, n_hyp))
+    live = done.cpu() == 0
+    for k in range(nb):
+        score = beam_scores[:, k] / (cur ** length_penalty)
+        worst, worst_i = hyp_score.min(dim=1)
+        slot = torch.where(n_hyp < nb, n_hyp.clamp(max=nb - 1).long(), worst_i)
+        ok = live & ((n_hyp < nb) | (score > worst))
+        sel = ok[:, None] & (torch.arange(nb)[None, :] == slot[:, None])                 # [B, nb]: the slot that takes the beam
+        hyp_score = torch.where(sel, score[:, None], hyp_score)
+        hyp_tok = torch.where(sel[:, :, None], cur_ids[:, k][:, None, :], hyp_tok)
+        hyp_len = torch.where(sel, torch.full_like(hyp_len, cur), hyp_len)
+        n_hyp = n_hyp + (ok & (n_hyp < nb)).to(i32)
+    best = hyp_score.argmax(dim=1)
+    ar_b = torch.arange(B)
+    out_tok, out_len = hyp_tok[ar_b, best], hyp_len[ar_b, best]
+    return [out_tok[b, :int(out_len[b])].to(dev) for b in range(B)]
+
+
+def _device_beams_ok(device_beams, dev, nb):
+    if device_beams is False:
+        return False
+    ok = dev.type == 'cuda' and 1 <= nb <= 8
+    if device_beams and not ok:
+        raise ValueError('device_beams=True needs logits on the GPU and 1 <= num_beams <= 8')
+    return ok
+
+
+@torch.no_grad()
 def beam_search(decoder, input_ids, attention_mask, enc, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
-                length_penalty=1.0, use_cache=True):
+                length_penalty=1.0, use_cache=True, device_beams=None, share_image=True):
     """decoder: prismer_amd RobertaForCausalLMModified (eval mode); enc: [B, S, Hv] encoder states (one row per image).
-    use_cache=False re-runs the full prefix every step like the reference (kept for the equivalence test)."""
+    use_cache=False re-runs the full prefix every step like the reference (kept for the equivalence test).
+    device_beams: None = the device beam step (beam_search_device) when the logits are bf16 on the GPU and num_beams <= 8, else the
+    tensor form; False forces the tensor form (beam_search_from_logits).  Cached and recomputing decoding take the same beam step.
+    share_image: the beams of an image share its cross-attention K/V and the prompt runs once per image; False tiles every image
+    num_beams times before anything runs (the earlier layout, kept for A/B measurements)."""
     B, T0 = input_ids.shape
     nb = num_beams
-    enc_b = enc.repeat_interleave(nb, dim=0).contiguous()
-    att0 = attention_mask.repeat_interleave(nb, dim=0)
+    on_device = _device_beams_ok(device_beams, input_ids.device, nb)
+    kw = dict(num_beams=nb, max_length=max_length, min_length=min_length, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+              length_penalty=length_penalty)
+    search = beam_search_device if on_device else beam_search_from_logits
+    att_b = torch.cat([attention_mask.repeat_interleave(nb, dim=0), attention_mask.new_ones(B * nb, max(max_length - T0, 0))], dim=1)
 
     def mask_for(T):                                               # generated positions are real tokens
-        if T == T0:
-            return att0
-        return torch.cat([att0, att0.new_ones(B * nb, T - T0)], dim=1)
+        return att_b[:, :T]
     if not use_cache:
+        enc_b = enc.repeat_interleave(nb, dim=0).contiguous()
+
         def step(ids):
             out = decoder(ids, attention_mask=mask_for(ids.shape[1]), encoder_hidden_states=enc_b, return_dict=True)
             return out.logits[:, -1, :]
-        return beam_search_from_logits(step, input_ids, nb, max_length, min_length, eos_token_id, pad_token_id, length_penalty)
-    prog, enc_bf = decoder.decoding_program(enc_b)
-    st = prog.decode_begin(enc_bf, max_length)
+        return search(step, input_ids, **kw)
+    if not share_image:
+        prog, enc_bf = decoder.decoding_program(enc.repeat_interleave(nb, dim=0).contiguous())
+        st = prog.decode_begin(enc_bf, max_length)
+
+        def step(ids):
+            T = ids.shape[1]
+            return prog.decode(st, ids, mask_for(T), 0 if T == T0 else T - 1)
+        return search(step, input_ids, reorder_fn=lambda rows: prog.decode_reorder(st, rows), **kw)
+    prog, enc_bf = decoder.decoding_program(enc)
+    st = prog.decode_begin(enc_bf, max_length, beams=nb)
+    nl = st['cache'][0].shape[0]
 
     def step(ids):
         T = ids.shape[1]
-        return prog.decode(st, ids, mask_for(T), 0 if T == T0 else T - 1)
-    return beam_search_from_logits(step, input_ids, nb, max_length, min_length, eos_token_id, pad_token_id, length_penalty,
-                                   reorder_fn=lambda rows: prog.decode_reorder(st, rows))
+        if T == T0:                                                # the prompt once per image: the beams of an item are identical here
+            return prog.decode(st, ids[::nb], attention_mask, 0)
+        return prog.decode(st, ids, mask_for(T), T - 1)
+    if on_device:                                                  # ph_beam_advance writes the gather index of the whole cache stack
+        return beam_search_device(step, input_ids, reorder_fn=lambda rows: prog.decode_reorder(st, rows), rows_rep=nl, **kw)
+    first = [True]
+
+    def step_tiled(ids):                                           # the tensor form wants one logit row per beam
+        lg = step(ids)
+        return lg.repeat_interleave(nb, dim=0) if lg.shape[0] == B else lg
+
+    def reorder(rows):                                             # ... and names source rows among B * nb: after the prefill they are B
+        prog.decode_reorder(st, rows // nb if first[0] else rows)
+        first[0] = False
+    return beam_search_from_logits(step_tiled, input_ids, reorder_fn=reorder, **kw)

@@ -728,6 +728,50 @@ def softmax_gather(logits, ids):
     return out
 
 
+def beam_topk_workspace(B, nb, V, device):
+    """the caller-owned scratch of beam_topk for B items x nb beams over V columns (either row layout), sized by ph_query_workspace"""
+    n = lib.ph_query_workspace(_lib.WS_BEAM_TOPK, (C.c_int64 * 3)(B, nb, V), 3)
+    if n < 0:
+        raise _lib.PrismerHipError(f'ph_query_workspace(PH_WS_BEAM_TOPK, {B}, {nb}, {V}): dimensions outside the limits of ph_beam_topk')
+    return torch.empty(n // 4, dtype=F32, device=device)
+
+
+def beam_topk(logits, beam_scores, B, nb, eos_token_id, ban_eos, workspace=None, out=None):
+    """The best 2*nb candidates of every item, best first: (top_score fp32, top_beam int32, top_tok int32), each [B, 2*nb], of
+    beam_scores[row] + log_softmax(logits[row]) over bf16 logit rows [B*nb or B, V] (a strided view is fine: row stride a multiple of 8
+    elements, rows 16-B aligned).  B rows = one row per item (all its beams share it, beam 0 is reported).  Ties: flat index ascending."""
+    assert logits.dim() == 2 and logits.dtype == BF16 and logits.stride(1) == 1 and beam_scores.dtype == F32 and beam_scores.is_contiguous()
+    R, V = logits.shape
+    assert R in (B, B * nb) and beam_scores.numel() == R, 'beam_topk: one logit row and one score per beam, or one per item'
+    if workspace is None:
+        workspace = beam_topk_workspace(B, nb, V, logits.device) if 1 <= nb <= 8 and V >= 2 * nb + 1 else torch.empty(1, dtype=F32, device=logits.device)
+    if out is None:
+        out = (torch.empty((B, 2 * nb), dtype=F32, device=logits.device), torch.empty((B, 2 * nb), dtype=torch.int32, device=logits.device),
+               torch.empty((B, 2 * nb), dtype=torch.int32, device=logits.device))
+    a = _lib.BeamTopkArgs(logits.data_ptr(), logits.stride(0), V, B, nb, R // B, beam_scores.data_ptr(), int(eos_token_id), int(bool(ban_eos)),
+                          workspace.data_ptr(), workspace.numel() * workspace.element_size(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+    check(lib.ph_beam_topk(C.byref(a), _stream()), 'ph_beam_topk')
+    return out
+
+
+def beam_advance(top, ids_in, ids_out, beam_scores, hyp_score, hyp_tok, hyp_len, n_hyp, done, rows_out, nb_in, cur, eos_token_id, pad_token_id,
+                 len_div):
+    """One step of the device-resident beam-search state from beam_topk's output `top` (see ph_beam_advance): ids_in -> ids_out with the new
+    token at `cur`, next beam_scores, finished hypotheses, done flags, and into rows_out (int32 [rep * B*nb]) the source row of every beam."""
+    top_score, top_beam, top_tok = top
+    B, nb = hyp_score.shape
+    Bb, Tmax = ids_in.shape
+    assert Bb == B * nb and ids_out.shape == ids_in.shape and ids_in.dtype == ids_out.dtype == hyp_tok.dtype == torch.int64
+    assert ids_in.is_contiguous() and ids_out.is_contiguous() and hyp_tok.is_contiguous() and hyp_tok.shape == (B, nb, Tmax)
+    assert top_score.shape == (B, 2 * nb) and beam_scores.numel() == Bb and beam_scores.dtype == hyp_score.dtype == F32
+    assert hyp_len.dtype == n_hyp.dtype == done.dtype == rows_out.dtype == top_beam.dtype == top_tok.dtype == torch.int32
+    assert hyp_len.numel() == Bb and n_hyp.numel() == B and done.numel() == B and rows_out.numel() % Bb == 0
+    a = _lib.BeamAdvanceArgs(top_score.data_ptr(), top_beam.data_ptr(), top_tok.data_ptr(), ids_in.data_ptr(), ids_out.data_ptr(), beam_scores.data_ptr(),
+                             hyp_score.data_ptr(), hyp_tok.data_ptr(), hyp_len.data_ptr(), n_hyp.data_ptr(), done.data_ptr(), rows_out.data_ptr(),
+                             B, nb, nb_in, Tmax, cur, int(eos_token_id), int(pad_token_id), rows_out.numel() // Bb, float(len_div))
+    check(lib.ph_beam_advance(C.byref(a), _stream()), 'ph_beam_advance')
+
+
 def ce_bwd(logits, labels, B, T, V, eps, row_lse, dloss):
     check(lib.ph_ce_bwd(logits.data_ptr(), logits.stride(0), labels.data_ptr(), B, T, V, logits.shape[1], eps, row_lse.data_ptr(),
                         dloss.data_ptr(), _stream()), 'ph_ce_bwd')

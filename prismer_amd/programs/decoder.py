@@ -294,24 +294,36 @@ class DecoderProgram:
     # prefix and re-projects the encoder output at every step.  Here the cross-attention K/V of all layers are projected ONCE per
     # image batch (the merged projection of the training path) and every self-attention layer keeps its K/V rows in a cache
     # [layers+1, rows, Tmax, 2H]; a step runs the new position(s) only.
-    def decode_begin(self, enc, Tmax):
-        """enc: [Bb, S, Hv] bf16 (already expanded to one row per beam).  Returns the decoding state."""
+    def decode_begin(self, enc, Tmax, beams=1):
+        """enc: [B, S, Hv] bf16, one row per image.  Returns the decoding state: the cross-attention K/V of the B images and a self-attention
+        cache of B * beams rows.  beams = 1: every row is its own image (rank inference; a caller that tiled enc itself).  beams > 1: the
+        `beams` hypotheses of an image are consecutive rows that share the image's K/V -- the prompt runs once per image (`decode` on B rows,
+        which fills cache rows 0 .. B-1) and the first `decode_reorder` (source row r // beams) hands its K/V to every beam row."""
         d = self.d
-        Bb, S, Hv = enc.shape
+        B, S, Hv = enc.shape
         H = d.hidden_size
-        enc2 = enc.reshape(Bb * S, Hv)
+        enc2 = enc.reshape(B * S, Hv)
         kvs, _ = self._project_kv(enc2, False)
         if self.kv_all is None:                          # per-layer linears: projected here, not inside every step's cross-attention
             kvs = [L['ca']['kv'].fwd(enc2) for L in self.layers]
         nl = len(self.layers) + 1
+        Bb = B * beams
         cache = [torch.zeros(nl, Bb, Tmax, 2 * H, dtype=BF16, device=enc.device) for _ in range(2)]     # ping-pong for beam reordering
-        return dict(kvs=kvs, cache=cache, cur=0, Bb=Bb, S=S, Tmax=Tmax, filled=0)
+        return dict(kvs=kvs, cache=cache, cur=0, Bb=Bb, B=B, beams=beams, S=S, Tmax=Tmax, filled=0)
 
     def decode_reorder(self, st, rows):
-        """beam step: hypothesis r continues former hypothesis rows[r] (int32 device tensor [Bb]) -- caches follow"""
+        """beam step: hypothesis r continues former hypothesis rows[r] (int32 device tensor [Bb]) -- caches follow.  rows of
+        (layers + 1) * Bb entries are taken as the gather index of the whole cache stack, l * Bb + source row (what ph_beam_advance writes
+        with rows_rep = layers + 1): no index arithmetic is launched then."""
         src, dst = st['cache'][st['cur']], st['cache'][st['cur'] ^ 1]
         nl, Bb, Tmax, W2 = src.shape
-        idx = (torch.arange(nl, device=rows.device, dtype=torch.int32)[:, None] * Bb + rows[None, :].to(torch.int32)).reshape(-1).contiguous()
+        if rows.numel() == nl * Bb and nl > 1:
+            assert rows.dtype == torch.int32
+            idx = rows
+        else:
+            if rows.dtype != torch.int32:
+                rows = rows.to(torch.int32)
+            idx = (torch.arange(nl, device=rows.device, dtype=torch.int32)[:, None] * Bb + rows[None, :]).reshape(-1).contiguous()
         ops.gather_rows(src.view(nl * Bb, Tmax * W2), idx, dst.view(nl * Bb, Tmax * W2), cols=st['filled'] * W2)
         st['cur'] ^= 1
 
@@ -326,9 +338,14 @@ class DecoderProgram:
         the caches and returns the logits of the LAST position, fp32 view [Bb, V] of a bf16 buffer."""
         d = self.d
         Bb, T = input_ids.shape
-        assert Bb == st['Bb'] and T <= st['Tmax'] and (t0 == 0 or t0 == T - 1), 'decode: prefill (t0=0) or single-token steps only'
+        nbm = st['beams']
+        # one row per beam; with beams > 1 the prefill (and only it) runs one row per image, into the first B rows of the cache
+        assert (Bb == st['Bb'] or (t0 == 0 and Bb == st['B'])) and T <= st['Tmax'] and (t0 == 0 or t0 == T - 1), \
+            'decode: prefill (t0=0) or single-token steps only'
         H, nh, Tmax = d.hidden_size, d.num_attention_heads, st['Tmax']
         Sq = T - t0
+        grouped = nbm > 1 and Bb == st['Bb']                                       # the beams of an image: ONE query block against its K/V
+        assert not grouped or Sq == 1, 'decode: beam rows run single-token steps (the prompt runs once per image)'
         key_mask = self._key_mask(attention_mask)
         h_all, _, _, hf_all = self._embed(input_ids)
         if t0 == 0:
@@ -338,13 +355,14 @@ class DecoderProgram:
             hf = hf_all.view(Bb, T, H)[:, t0:].reshape(Bb * Sq, H).contiguous()
 
         def attend(li, qkv):                                                      # qkv [Bb*Sq, 3H]
-            cache = st['cache'][st['cur']][li]                                    # [Bb, Tmax, 2H]
+            cache = st['cache'][st['cur']][li][:Bb]                               # [Bb, Tmax, 2H]
             # K | V rows of the new positions -> cache[:, t0:T]
             ops.copy_rows(qkv[:, H:], cache.view(Bb * Tmax, 2 * H), Bb * Sq, 2 * H, dst_map=ops.RowMap(Sq, Tmax, t0), src_ld=3 * H, dst_ld=2 * H)
             cs = (Tmax * 2 * H, 2 * H)
             return ops.attention_fwd(qkv[:, :H], cache[:, :, :H], cache[:, :, H:], Bb, nh, Sq, T, H // nh, q_strides=(Sq * 3 * H, 3 * H),
                                      k_strides=cs, v_strides=cs, key_mask=key_mask, causal=Sq > 1) + (None,)
-        h, hf = self._layers(h, hf, attend, self._cached_cross(st, Bb, Sq), None, None)
+        cross = self._cached_cross(st, st['B'], nbm) if grouped else self._cached_cross(st, Bb, Sq)
+        h, hf = self._layers(h, hf, attend, cross, None, None)
         st['filled'] = max(st['filled'], T)
         st['key_mask'] = key_mask                                                # (the prefix key mask of score_continuations)
         last = h if Sq == 1 else h.view(Bb, Sq, H)[:, -1].contiguous()           # LM head on the last position only

@@ -1,0 +1,160 @@
+"""inference='generate' at the reference's eval configurations (3 beams): the parent layout -- every image tiled num_beams times, beam step as
+stock tensor ops (beam_search(device_beams=False, share_image=False)) -- against the new path -- one image's K/V shared by its beams, prompt once
+per image, beam step in the library (ph_beam_topk, ph_beam_advance) -- in one process, alternating, device-synchronised, after a warm-up of both.
+Per arm: ms per generate call (median over all calls, and the medians of the two halves of the calls: their distance is the spread a
+difference between the arms has to exceed), the peak memory the call adds (torch.cuda.max_memory_allocated), kernels per decode step, and whether
+the returned token lists agree (reported, not asserted: at random-init BASE weights near-ties flip).
+Kernels per step: one extra call per arm under torch.profiler; every device kernel event is counted, those whose name carries `at::` (ATen's
+namespaces) or is a copy / fill of the runtime as torch's, the rest as the library's; divided by the decode steps of the call (prefill included).
+ph_prof_collect's count of library ENTRY-POINT calls is printed beside it (some entry points launch two kernels).
+Prismer-BASE decoder with synthetic weights, random encoder states of the leg's length (S = (res / 16)^2 + 64 resampler latents).
+    python tools/generate_probe.py [--reps N] [--out FILE]        all legs
+    python tools/generate_probe.py --profile [--arm new|parent]   one warm-up + one call of the first leg (for rocprofv3 --kernel-trace --stats)"""
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from prismer_amd import _lib, config, synth
+from prismer_amd.model.generate import beam_search
+from prismer_amd.model.prismer import _Cfg
+from prismer_amd.modules.roberta import RobertaForCausalLMModified
+
+NB = 3
+# (name, resolution, images, prompt tokens (padded), ragged prompts, max_length, min_length, length_penalty)
+LEGS = [('caption 480^2 B=32', 480, 32, 4, False, 20, 8, 1.0),             # prismer_caption.py:45-50: prompt 'A picture of', max_length 20, min_length 8
+        ('vqa 480^2 B=32', 480, 32, 25, True, 35, 1, -1.0),                # prismer_vqa.py:52-58: questions padded to the longest, + 10 tokens, lp -1
+        ('caption 224^2 B=32', 224, 32, 4, False, 20, 8, 1.0)]
+ARMS = [('parent', dict(device_beams=False, share_image=False)), ('new', dict())]
+
+
+def inputs(d, B, Tq, ragged, res, seed):
+    g = torch.Generator().manual_seed(seed)
+    S = (res // 16) ** 2 + 64
+    enc = (torch.randn(B, S, d.vision_hidden_size, generator=g) * 0.5).to(torch.bfloat16).cuda()
+    q = torch.randint(3, d.vocab_size, (B, Tq), generator=g); q[:, 0] = d.bos_token_id
+    qa = torch.ones(B, Tq, dtype=torch.long)
+    if ragged:
+        for b in range(B):                                              # ragged questions, right-padded to Tq
+            L = Tq - (b * 5) % max(Tq - 3, 1)
+            q[b, L:] = d.pad_token_id; qa[b, L:] = 0
+    return enc, q.cuda(), qa.cuda(), S
+
+
+def call(dec, d, enc, q, qa, leg, kw):
+    _, _, _, _, _, Tmax, Tmin, lp = leg
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    before = torch.cuda.memory_allocated()
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        out = beam_search(dec, q, qa, enc, num_beams=NB, max_length=Tmax, min_length=Tmin, eos_token_id=d.eos_token_id, pad_token_id=d.pad_token_id,
+                          length_penalty=lp, **kw)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    return ms, torch.cuda.max_memory_allocated() - before, [o.tolist() for o in out]
+
+
+def median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def kernels_per_step(dec, d, enc, q, qa, leg, kw):
+    """(torch kernels, library kernels, library entry-point calls) per decode step of one call"""
+    from torch.profiler import ProfilerActivity, profile
+    steps = leg[5] - leg[3]
+    _lib.lib.ph_prof_enable(1)
+    buf = (C.c_double * 32)()
+    _lib.lib.ph_prof_collect(buf)                                          # reset
+    call(dec, d, enc, q, qa, leg, kw)
+    _lib.lib.ph_prof_collect(buf)
+    _lib.lib.ph_prof_enable(0)
+    entry = sum(buf[4 * f + 3] for f in range(8))
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        call(dec, d, enc, q, qa, leg, kw)
+    n_torch = n_lib = 0
+    for ev in prof.key_averages():
+        if str(getattr(ev, 'device_type', '')).endswith('CUDA') or getattr(ev, 'is_legacy', False):
+            name = ev.key
+            if 'at::' in name or 'Memcpy' in name or 'Memset' in name or 'memcpy' in name or 'fillBuffer' in name or 'copyBuffer' in name:
+                n_torch += ev.count
+            else:
+                n_lib += ev.count
+    return n_torch / steps, n_lib / steps, entry / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=12)
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--profile', action='store_true')
+    ap.add_argument('--arm', default='new', choices=['new', 'parent'])
+    ap.add_argument('--no-kernel-count', action='store_true')
+    args = ap.parse_args()
+    d = config.prismer_base()
+    dec = RobertaForCausalLMModified(_Cfg(d.roberta_config_dict()))
+    dec.load_state_dict(synth.synth_decoder_state(d, 0))
+    dec.cuda().eval()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    if args.profile:
+        leg = LEGS[0]
+        enc, q, qa, _ = inputs(d, leg[2], leg[3], leg[4], leg[1], 0)
+        kw = dict(ARMS)[args.arm]
+        call(dec, d, enc, q, qa, leg, kw)
+        ms, _, _ = call(dec, d, enc, q, qa, leg, kw)
+        print(f'profile: one {args.arm} generate call, {leg[0]}: {ms:.2f} ms')
+        return
+    reps = max(args.reps, 10)
+    props = torch.cuda.get_device_properties(0)
+    say(f'device: {props.name}, {props.total_memory / 2**30:.0f} GiB; Prismer-BASE decoder (synthetic weights), random encoder states, {NB} beams')
+    say(f'parent = beam_search(device_beams=False, share_image=False): images tiled {NB}x, tensor-op beam step;  new = shared image K/V, device beam step')
+    say(f'{"leg":20s} {"arm":7s} {"ms/call median":>15s} {"half medians":>19s} {"spread":>8s} {"peak added":>11s} {"kernels/step torch | library (entry calls)":>44s}')
+    for li, leg in enumerate(LEGS):
+        name, res, B, Tq, ragged = leg[:5]
+        enc, q, qa, S = inputs(d, B, Tq, ragged, res, li)
+        res_ = {a: call(dec, d, enc, q, qa, leg, kw) for a, kw in ARMS}            # warm-up of both
+        times = {a: [] for a, _ in ARMS}
+        for _ in range(reps):                                              # alternating
+            for a, kw in ARMS:
+                r = call(dec, d, enc, q, qa, leg, kw)
+                times[a].append(r[0])
+                res_[a] = r
+        spread = {}
+        for a, kw in ARMS:
+            t = times[a]
+            h0, h1 = median(t[:len(t) // 2]), median(t[len(t) // 2:])
+            spread[a] = abs(h0 - h1)
+            if args.no_kernel_count:
+                kc = 'not counted'
+            else:
+                try:
+                    kt, kl, ke = kernels_per_step(dec, d, enc, q, qa, leg, kw)
+                    kc = f'{kt:7.1f} | {kl:7.1f} ({ke:6.1f})'
+                except Exception as e:                                     # the profiler is a measuring aid, not a product path
+                    kc = f'profiler unavailable: {type(e).__name__}: {e}'[:60]
+            say(f'{name:20s} {a:7s} {median(t):15.2f} {h0:9.2f} {h1:9.2f} {spread[a]:8.2f} {res_[a][1] / 2**20:7.0f} MiB {kc:>44s}')
+        same = sum(x == y for x, y in zip(res_['parent'][2], res_['new'][2]))
+        mp, mn = median(times['parent']), median(times['new'])
+        Hh, L = d.hidden_size, d.num_hidden_layers
+        say(f'{name:20s} S = {S}: cross-attention K/V {B * NB * S * 2 * Hh * L * 2 / 2**20:.0f} MiB tiled, {B * S * 2 * Hh * L * 2 / 2**20:.0f} MiB shared; '
+            f'parent / new = {mp / mn:.2f}x (medians; difference {mp - mn:.2f} ms against a spread of {max(spread.values()):.2f} ms); '
+            f'token lists agree for {same}/{B} items')
+        del enc, q, qa, res_
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
