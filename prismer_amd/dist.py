@@ -76,17 +76,21 @@ def rs_chunk(n, world):
 
 class GradExchange:
     def __init__(self, world, all_reduce, pack=None, unpack=None, payload='fp32', chunk_elems=64 << 20, comm_stream=None,
-                 transport='torch.distributed', mode='allreduce', rank=0, reduce_scatter=None, all_gather=None, event_factory=None):
+                 transport='torch.distributed', mode='allreduce', rank=0, reduce_scatter=None, all_gather=None, event_factory=None, accum=1):
         """all_reduce(t): in-place SUM over ranks, enqueued on the CURRENT stream (torch: dist.all_reduce; native:
         ph_allreduce_bucket).  pack(src_f32, dst_bf16, scale) / unpack(src_bf16, dst_f32): cast kernels (bf16 payload only).
         mode 'rs_ag': reduce_scatter(out[c], inp[world * c]) and all_gather(out[world * c], inp[c]) (torch:
-        dist.reduce_scatter_tensor / all_gather_into_tensor)."""
+        dist.reduce_scatter_tensor / all_gather_into_tensor).
+        accum: gradient accumulation steps of the Trainer -- what is exchanged (once per UPDATE) is the sum over `accum` micro-batches, so the
+        average is 1/(world * accum): the bf16 payload's pre-scale, or the fp32 payload's post_scale."""
         assert payload in ('bf16', 'fp32') and mode in ('allreduce', 'rs_ag')
         self.world, self.all_reduce, self.pack, self.unpack = world, all_reduce, pack, unpack
         self.payload, self.chunk, self.comm_stream, self.transport = payload, chunk_elems, comm_stream, transport
         self.mode, self.rank, self.reduce_scatter, self.all_gather = mode, rank, reduce_scatter, all_gather
         # what is left of the 1/world average after the exchange: the bf16 payload is pre-scaled, the fp32 one (DDP's) is not
-        self.post_scale = 1.0 if payload == 'bf16' else 1.0 / world
+        self.accum = int(accum)
+        self.pre_scale = 1.0 / (world * self.accum)
+        self.post_scale = 1.0 if payload == 'bf16' else 1.0 / (world * self.accum)
         self.scratch = {}          # id(flat) -> bf16 bucket buffer of the same length
         self.stage = {}            # (id(flat), lo) -> (staging buffer [world * c], reduced chunk [c])  (rs_ag)
         self.owned = {}            # id(flat) -> {lo: (a, b)}: the piece of range [lo, hi) this rank owns after the reduce-scatter
@@ -148,7 +152,7 @@ class GradExchange:
                 for a, b in bucket_ranges(hi, self.chunk, lo):
                     if self.payload == 'bf16':
                         buf = self._bucket(flat)
-                        self.pack(flat[a:b], buf[a:b], 1.0 / self.world)
+                        self.pack(flat[a:b], buf[a:b], self.pre_scale)
                         self.all_reduce(buf[a:b])
                         self.unpack(buf[a:b], flat[a:b])
                         self.bytes_per_step += 2 * (b - a)
@@ -178,7 +182,7 @@ class GradExchange:
             self.stage[key] = (torch.zeros(W * c, dtype=dt, device=flat.device), torch.empty(c, dtype=dt, device=flat.device))
         stage, red = self.stage[key]
         if self.payload == 'bf16':
-            self.pack(flat[lo:hi], stage[:n], 1.0 / W)                  # (the pad tail of the staging buffer stays zero)
+            self.pack(flat[lo:hi], stage[:n], self.pre_scale)                  # (the pad tail of the staging buffer stays zero)
         else:
             _copy_flat(stage[:n], flat[lo:hi])
         self.reduce_scatter(red, stage)

@@ -945,6 +945,15 @@ def zeros(shape, dtype, device):
     return buf[:nbytes].view(dtype).reshape(shape)
 
 
+def fill_zero(t):
+    """t[:] = 0 for a contiguous, 16-B aligned tensor of a multiple of 16 bytes (the flat gradient buffers): ONE ph_fill_zero launch, what a
+    captured segment uses instead of Tensor.zero_() (a memset node)"""
+    nbytes = t.numel() * t.element_size()
+    assert t.is_contiguous() and nbytes % 16 == 0 and t.data_ptr() % 16 == 0, 'ops.fill_zero: need a contiguous 16-B aligned buffer of a multiple of 16 bytes'
+    check(lib.ph_fill_zero(t.data_ptr(), nbytes, _stream()), 'ph_fill_zero')
+    return t
+
+
 def copy_flat(dst, src):
     """dst[:] = src for contiguous 1-D tensors of one dtype: ph_copy_bytes for the 16-B aligned body, Tensor.copy_ for a ragged tail / head"""
     assert dst.dtype == src.dtype and dst.numel() == src.numel() and dst.is_contiguous() and src.is_contiguous()

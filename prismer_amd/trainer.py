@@ -37,11 +37,50 @@ F32, BF16 = torch.float32, torch.bfloat16
 from .schedules import cosine_lr                          # noqa: E402  (utils.py:13-17 of the reference; re-exported)
 
 
+def accum_plan(k, j, u=0, world=1):
+    """Bookkeeping of micro-step j (0-based) of update u (0-based) under Trainer(accum_steps=k), as a pure function (the Trainer and
+    tests/test_accum_logic_cpu.py both read it):
+      graph        which captured program runs: 'whole' (k = 1: forward, backward, both AdamW launches -- the one graph of a plain step), 'open'
+                   (first micro-step of a group: single-writer weight gradients overwritten), 'middle' (everything accumulates), 'close' (a middle
+                   micro-step followed by both AdamW launches); k = 2 uses 'open' + 'close' only
+      overwrite    the single-writer set (ops.WQ.exclusive) is active
+      update       the step ends in AdamW;  exchanges: the step hands gradients to the exchange (N ranks; DDP's no_sync otherwise)
+      avg_scale    the factor between the summed gradient buffers and the update gradient, 1 / (world k), applied once in fp32
+      seed_index   the dropout seed is splitmix64^seed_index of the start seed;  lr_index: the schedule position;  bias_step: Adam's t"""
+    assert k >= 1 and 0 <= j < k
+    update = j == k - 1
+    graph = 'whole' if k == 1 else 'open' if j == 0 else 'close' if update else 'middle'
+    return dict(graph=graph, overwrite=j == 0, update=update, exchanges=update and world > 1, avg_scale=1.0 / (world * k),
+                seed_index=u * k + j, lr_index=u, bias_step=u + 1)
+
+
 class Trainer:
     def __init__(self, model, lr=5e-5, weight_decay=0.05, betas=(0.9, 0.999), eps=1e-8, min_lr=0.0, total_steps=1000,
                  task='caption', use_graph=True, process_group=None, bucket_mb=64, side_stream=False, micro_batches=1, keep_grads=False,
                  max_text_len=None, grad_payload='fp32', transport='torch.distributed', dec_backward_stages=3, lr_schedule=None,
-                 shard_optimizer=False, overwrite_single_writer=True, allow_eager_fallback=False, broadcast_buffers=False, exchange_issue='device'):
+                 shard_optimizer=False, overwrite_single_writer=True, allow_eager_fallback=False, broadcast_buffers=False, exchange_issue='device',
+                 accum_steps=1):
+        """accum_steps=k > 1: gradient accumulation.  k consecutive step() calls form one GROUP: each runs forward + backward on the bound
+        micro-batch (fixed size B, its own BatchNorm batch statistics, dropout masks and instance draws), the k-th also applies ONE AdamW update
+        with the mean gradient of the group -- the reference loop (train_caption.py:126-135) written as
+            cosine_lr_schedule(optimizer, u, ...); optimizer.zero_grad(); for j in 1..k: (model(b_j) / k).backward(); optimizer.step()
+        which is also what k DDP replicas of batch B compute (no SyncBN in the reference).  `it`, the LR schedule position, `total_steps` and Adam's
+        bias corrections count UPDATES; the dropout seed, BatchNorm running statistics / counters and the instance table advance per micro-step.
+        The 1/k is applied once, in fp32, as AdamW's grad_scale; with keep_grads=True the gradient buffers after the k-th micro-step hold the plain
+        fp32 SUM over the group (divide by k to get the update gradient).  step() returns the bound micro-batch's loss; `group_loss` is the mean
+        loss of the last completed group (device tensor).  `micro_index` is the position inside the open group; state_dict() is refused inside
+        one; abort_group() drops an open group (the next step() opens a fresh one from zero-filled buffers), and an exception inside step() does
+        the same.  Captured form: an opening micro-step (single-writer weight gradients overwritten), a middle one (everything accumulates) and a
+        closing one (a middle micro-step + both AdamW launches), three graphs over ONE memory pool; accum_steps=1 is the single graph it was.
+        N ranks: non-closing micro-steps exchange nothing (DDP's no_sync), the closing one runs the staged schedule on the accumulated sum."""
+        self.accum = int(accum_steps)
+        if self.accum < 1:
+            raise ValueError('accum_steps must be >= 1')
+        if self.accum > 1 and shard_optimizer:
+            raise ValueError('accum_steps > 1 with shard_optimizer is not supported (the sharded tails re-zero and exchange per step)')
+        if self.accum > 1 and side_stream and micro_batches > 1:
+            raise ValueError('accum_steps > 1 with the eager micro_batches experiment is not supported (micro_batches cuts ONE batch into parallel '
+                             'branches; accum_steps is the gradient accumulation over several batches)')
         self.model = model
         self.enc, self.dec = model.expert_encoder, model.text_decoder
         self.init_lr, self.min_lr, self.total_steps = lr, min_lr, total_steps
@@ -58,6 +97,7 @@ class Trainer:
             self.world = torch.distributed.get_world_size(process_group)
         self.it = 0
         self.graphs = None
+        self._micro = 0                        # position inside the open accumulation group (micro_index)
         # How a finished stage's gradients reach the communication stream (N > 1, graph replay):
         #   'device' (default): the communication stream waits for an event of the compute stream (round 1-6 behaviour);
         #   'host': the NEXT segment is enqueued first, then the host waits for the stage's event and launches the collectives with no
@@ -97,6 +137,12 @@ class Trainer:
         self.v = [torch.zeros(max(hi - lo, 1), dtype=F32, device=dev) for lo, hi in own]
         self.piece_state = {}                                  # rs_ag: (store index, a, b) -> (m, v)
         self.hyper = torch.zeros(3, dtype=F32, device=dev)
+        # accumulation group: [running sum of loss / k, this micro-step's loss / k, their sum] and the mean loss of the last COMPLETED group
+        # (written by the closing micro-step only: the replays of the next group leave it alone)
+        self._loss_acc = torch.zeros(3, dtype=F32, device=dev)
+        self._table_pad = torch.zeros(1, dtype=F32, device=dev)      # float word of a table-only ph_store_words launch (_host_prologue)
+        self._group_loss = torch.zeros(1, dtype=F32, device=dev)
+        self._kind_loss = {}
         # per-step host values (learning rate, Adam bias corrections, instance draws) travel in the arguments of one tiny kernel
         # (ops.store_words): stream-ordered like the copies they replace, no pinned staging, no copy engine
         self.table = torch.zeros(256, dtype=torch.int32, device=dev)
@@ -206,7 +252,7 @@ class Trainer:
         return GradExchange(self.world, reduce_fn, pack=lambda src, dst, scale=1.0: ops.cast_to_bf16(src, out=dst, scale=scale),
                             unpack=lambda src, dst: ops.cast_to_f32(src, out=dst), payload=payload, chunk_elems=self.bucket_elems,
                             comm_stream=self.comm_stream, transport='rccl via ' + ('prismer_comm (native)' if transport == 'native' else 'torch.distributed'),
-                            mode='rs_ag' if self.rs_ag else 'allreduce', rank=self.rank, reduce_scatter=rs_fn, all_gather=ag_fn)
+                            mode='rs_ag' if self.rs_ag else 'allreduce', rank=self.rank, reduce_scatter=rs_fn, all_gather=ag_fn, accum=self.accum)
 
     AUTO_BUSBW_GB_S = 150.0          # below this measured all-reduce bus bandwidth the fp32 payload no longer hides behind the backward
 
@@ -445,15 +491,18 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------------ single-writer weight gradients
     @contextlib.contextmanager
-    def _wq_scope(self):
+    def _wq_scope(self, opening=True):
         """Brackets one whole step (eager, capture warm-up or capture).  The first bracketed step COUNTS the deferred weight-gradient
         GEMMs per output; outputs inside the flat gradient buffers that are written exactly once per step are from then on
         OVERWRITTEN by their GEMM (accumulate = 0: no read of the zeroed buffer) and kept out of AdamW's zero_grad stores (keep bitmap,
         whole 1024-element chunks only) -- 0.9 GB less read and 0.9 GB less written per step at Prismer-BASE.  Everything else
         (embeddings, biases, LayerNorm / BatchNorm parameters, conv weights, tied or micro-batched weights) keeps accumulate-into-zero.
-        Trainer(overwrite_single_writer=False) switches it off."""
+        Trainer(overwrite_single_writer=False) switches it off.
+        opening=False (accum_steps > 1, every micro-step of a group but the first): the buffers hold the group's partial sums, so EVERY producer
+        accumulates -- the exclusive set is empty and nothing is counted (the count of the opening micro-step holds for the configuration)."""
         wq = ops.WQ
-        if not self._overwrite:
+        if not self._overwrite or not opening:
+            wq.counts, wq.exclusive = None, None
             yield
             return
         if self._exclusive is not None and self._count_config != self._wq_config():
@@ -478,7 +527,7 @@ class Trainer:
 
     def _wq_config(self):
         """what the frozen single-writer state depends on: a change invalidates it (see _wq_scope)"""
-        return (bool(ops.WQ.enabled), self.micro, self.keep_grads, tuple(st.n_train for st in self.stores))
+        return (bool(ops.WQ.enabled), self.micro, self.keep_grads, tuple(st.n_train for st in self.stores), self.accum)
 
     def _finish_count(self, counts):
         excl = set()
@@ -504,8 +553,9 @@ class Trainer:
         self._exclusive, self._keep_maps = excl, maps
 
     def _post_scale(self):
-        """what is left of DDP's 1/world average after the exchange (1/world for the fp32 SUM, 1 for the pre-scaled bf16 payload)"""
-        return 1.0 if self.exchange is None else self.exchange.post_scale
+        """what is left of the 1/(world * accum_steps) average after the exchange: all of it for the fp32 SUM (and for one rank), 1 for the
+        pre-scaled bf16 payload.  Applied in fp32 by the fused AdamW (grad_scale)."""
+        return 1.0 / self.accum if self.exchange is None else self.exchange.post_scale
 
     def _adamw_rs(self, i):
         """rs_ag: AdamW on the pieces of store i this rank received from the reduce-scatters, all-gather of the updated fp32
@@ -578,7 +628,66 @@ class Trainer:
         ops.advance_seed(self.seed)
         self._grads_clean = False
 
-    def _schedule(self):
+    # ------------------------------------------------------------------------------------------ accumulation group (accum_steps > 1)
+    @property
+    def micro_index(self):
+        """position inside the open accumulation group: 0 .. accum_steps - 1 (0 = at a group boundary)"""
+        return self._micro
+
+    @property
+    def group_loss(self):
+        """device tensor [1]: mean loss of the last completed group (accum_steps = 1: the last step's loss)"""
+        return self._group_loss if self.accum > 1 else self.loss_buf
+
+    def _kinds(self):
+        return [accum_plan(self.accum, j)['graph'] for j in sorted({0, min(1, self.accum - 1), self.accum - 1})]
+
+    def abort_group(self):
+        """drops the open group (its partial sums are discarded: the next step() opens a fresh group on zero-filled buffers).  Dropout seed,
+        BatchNorm statistics and instance draws of the micro-steps already run are not rolled back; `it` did not move."""
+        if self._micro:
+            self._micro = 0
+            self._grads_clean = False
+
+    def _zero_grads(self):
+        for st in self.stores:
+            if st.n_train:
+                ops.fill_zero(st.grad)
+
+    def _micro_begin(self, opening):
+        """in front of a micro-step's forward (captured with it): optimizer.zero_grad() where the previous update did not leave the buffers
+        clean -- in the OPENING micro-step only -- as a kernel, never a memset node; _seg_forward's own fill is switched off"""
+        if opening and not self._grads_clean:
+            self._zero_grads()
+        self._grads_clean = True
+
+    def _micro_loss(self, kind):
+        """group loss in three one-block launches (no stock torch kernel in a captured segment): acc <- acc + loss / k through a scratch word
+        (inputs and output of a launch never alias), the closing micro-step publishes the mean"""
+        a = self._loss_acc
+        self._kind_loss[kind] = self.loss_buf                  # (one output buffer per graph: all stay referenced, the shared pool cannot recycle them)
+        if kind == 'open':
+            ops.weighted_sum(self.loss_buf, None, 1.0 / self.accum, out=a[0:1])
+            return
+        ops.weighted_sum(self.loss_buf, None, 1.0 / self.accum, out=a[1:2])
+        ops.weighted_sum(a[0:2], None, 1.0, out=a[2:3])
+        ops.weighted_sum(a[2:3], None, 1.0, out=self._group_loss if kind == 'close' else a[0:1])
+
+    def _seg_micro(self, kind):
+        """a whole non-closing micro-step as ONE segment: forward, decoder backward, encoder backward, seed advance; no optimizer, no exchange"""
+        self._micro_begin(kind == 'open')
+        self._seg_forward(self.static, (len(self.dec_prog.layers), 0))
+        self._micro_loss(kind)
+        self._seg_enc_trunk_backward()
+        self._seg_enc_front_backward()
+        ops.advance_seed(self.seed)
+
+    def _seg_close_first(self, dec_hi_lo):
+        self._micro_begin(False)
+        self._seg_forward(self.static, dec_hi_lo)
+        self._micro_loss('close')
+
+    def _schedule(self, kind='whole'):
         """[(compute segment, host action right after it)].
         One rank: the whole step is ONE segment (forward, decoder backward, encoder backward, both AdamW launches, seed advance).
         Data parallel: the backward is cut in reverse layer order -- decoder in `len(dec_cuts) - 1` stages, encoder trunk,
@@ -586,17 +695,20 @@ class Trainer:
         the last one (the stems' 25 M parameters) is exchanged on the critical path; the decoder's AdamW runs on the
         optimizer stream as soon as its buckets are reduced."""
         s = self.static
+        if kind in ('open', 'middle'):
+            return [(lambda: self._seg_micro(kind), None)]
+        first = self._seg_forward if kind == 'whole' else (lambda s, hi_lo: self._seg_close_first(hi_lo))      # ('close': the accumulating forms)
         if self.world == 1:
             nl = len(self.dec_prog.layers)
 
             def whole_step():                  # ONE captured graph (round 6: three replays per step cost 0.18 ms in launch gaps, tools/stream_edge_probe.py's box)
-                self._seg_forward(self.static, (nl, 0))
+                first(self.static, (nl, 0))
                 self._seg_enc_backward_with_dec_adamw()
                 self._seg_optimizer_tail()
             return [(whole_step, None)]
         cuts = self.dec_cuts
         nst = len(cuts) - 1
-        sched = [(lambda: self._seg_forward(self.static, (cuts[0], cuts[1])), lambda: self._issue('dec0'))]
+        sched = [(lambda: first(self.static, (cuts[0], cuts[1])), lambda: self._issue('dec0'))]
         for k in range(1, nst):
             sched.append(((lambda k=k: self._seg_dec_backward(cuts[k], cuts[k + 1])), (lambda k=k: self._issue(f'dec{k}'))))
         seg, host = sched[-1]
@@ -618,6 +730,13 @@ class Trainer:
         """per-step host work: LR schedule (cosine per ITERATION, train_caption.py:127), Adam bias corrections and the
         instance-embedding draw table (vit.py:145-147: Python `random`), shipped in the arguments of one kernel launch (round 6: the two pinned
         copies they used to ride queued behind a loader's host-to-device prefetch on the copy engine)."""
+        if self.accum > 1 and self._micro != self.accum - 1:
+            # a non-closing micro-step: only the instance table is drawn (per forward, i.e. per micro-batch); `it`, the schedule position and
+            # the bias corrections belong to the UPDATE and move with the closing micro-step.  (ph_store_words wants at least one float
+            # word: it goes to a pad word of its own that nothing reads.)
+            if 'obj_detection' in self.enc.experts:
+                ops.store_words(self._table_pad, (0.0,), self.table, [random.randint(0, 127) for _ in range(256)])
+            return
         self.it += 1
         lr = self.lr_schedule(self.it - 1)
         hyper = (lr, 1.0 - self.betas[0] ** self.it, 1.0 - self.betas[1] ** self.it)
@@ -750,7 +869,8 @@ class Trainer:
         return dict(master=[st.master.clone() for st in self.stores], m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
                     bufs=[b.clone() for mod in (self.enc, self.dec) for b in mod.buffers()], seed=self.seed.clone(), it=self.it,
                     rng=random.getstate(), grads=[st.grad.clone() for st in self.stores], clean=self._grads_clean,
-                    pieces={k: (m.clone(), v.clone()) for k, (m, v) in self.piece_state.items()})
+                    pieces={k: (m.clone(), v.clone()) for k, (m, v) in self.piece_state.items()},
+                    micro=self._micro, step_open=self._step_open, loss_acc=self._loss_acc.clone(), group_loss=self._group_loss.clone())
 
     def _restore(self, snap):
         for st, t in zip(self.stores, snap['master']):
@@ -768,6 +888,8 @@ class Trainer:
             self.piece_state[k][0].copy_(m); self.piece_state[k][1].copy_(v)
         self.seed.copy_(snap['seed'])
         self.it, self._grads_clean = snap['it'], snap['clean']
+        self._micro, self._step_open = snap['micro'], snap['step_open']
+        self._loss_acc.copy_(snap['loss_acc']); self._group_loss.copy_(snap['group_loss'])
         random.setstate(snap['rng'])
 
     def _capture(self):
@@ -776,10 +898,27 @@ class Trainer:
         the first replayed step is then update-for-update the first eager step (one AdamW update per batch like the
         reference loop, train_caption.py:126-135)."""
         snap = self._snapshot()
+        try:
+            self._capture_from(snap)
+        except BaseException:
+            # a failed warm-up or capture (allow_eager_fallback continues eagerly) must not leave the warm-up's state behind: the position
+            # inside the group (the warm-up sets it per kind), `it`, the half-updated model
+            torch.cuda.synchronize()
+            self._restore(snap)
+            self.graphs, self._graph_no_fill = None, False
+            raise
+
+    def _capture_from(self, snap):
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):                           # warm-up outside capture (allocations, lazily built shadows)
             for _ in range(2):
+                if self.accum > 1:                              # one micro-step of every captured kind, in group order: open [, middle], close
+                    for kind in self._kinds():
+                        self._micro = {'open': 0, 'middle': 1, 'close': self.accum - 1}[kind]
+                        self._host_prologue()
+                        self._run_eager(kind)
+                    continue
                 self._host_prologue()
                 with self._wq_scope():                          # (pass 1 counts the writers, pass 2 already overwrites)
                     for seg, coll in self._schedule():
@@ -796,6 +935,8 @@ class Trainer:
                 st.grad.zero_()
             self._grads_clean = True
             self._graph_no_fill = True                          # the replayed step relies on its predecessor's AdamW for clean buffers
+        elif self.accum > 1:
+            self._grads_clean = False                           # the opening graph carries the fill (a kernel: Trainer._micro_begin)
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         # thread_local: RCCL's watchdog thread polls events while we capture (world > 1); only this thread's calls are policed
@@ -809,16 +950,37 @@ class Trainer:
         gc_was = gc.isenabled()
         gc.disable()
         try:
-            with self._wq_scope():
-                for seg, coll in self._schedule():
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, pool=pool, **mode):
-                        seg()
-                    graphs.append((g, coll))
+            if self.accum > 1:
+                # one graph list per kind of micro-step, ONE memory pool: a micro-step's activations are dead when its last segment ends, so the
+                # kinds reuse each other's blocks and may replay in any order
+                graphs = {}
+                for kind in self._kinds():
+                    graphs[kind] = []
+                    with self._wq_scope(opening=kind == 'open'):
+                        for seg, coll in self._schedule(kind):
+                            g = torch.cuda.CUDAGraph()
+                            with torch.cuda.graph(g, pool=pool, **mode):
+                                seg()
+                            graphs[kind].append((g, coll))
+            else:
+                with self._wq_scope():
+                    for seg, coll in self._schedule():
+                        g = torch.cuda.CUDAGraph()
+                        with torch.cuda.graph(g, pool=pool, **mode):
+                            seg()
+                        graphs.append((g, coll))
         finally:
             if gc_was:
                 gc.enable()
         self.graphs = graphs
+
+    def _run_eager(self, kind):
+        with self._wq_scope(opening=kind in ('whole', 'open')):
+            for i, (seg, coll) in enumerate(self._schedule(kind)):
+                self.trace.append(('seg', i))
+                seg()
+                if coll is not None:
+                    coll()
 
     def step(self):
         """one optimisation step on the bound batch; returns the (device) scalar loss tensor without synchronising."""
@@ -837,19 +999,37 @@ class Trainer:
                 torch.cuda.synchronize()
                 self.graphs, self.use_graph = None, False
                 ops.join_side()
+        if self.accum > 1:
+            it0 = self.it
+            try:
+                return self._step_body()
+            except BaseException:
+                # an exception anywhere in a micro-step (a host hook, a collective) ends the GROUP: its partial sums never reach the AdamW that
+                # re-zeroes them, the next step() opens a fresh group and (replay: _step_open) fills the buffers first
+                self.it = it0
+                self._micro = 0
+                self._grads_clean = False
+                raise
+        return self._step_body()
+
+    def _step_body(self):
+        plan = accum_plan(self.accum, self._micro, world=self.world)
+        opening, closing, kind = plan['overwrite'], plan['update'], plan['graph']
         self._host_prologue()
         if self.broadcast_buffers:
             self.sync_buffers()
-        if self.exchange is not None:
+        if self.exchange is not None and closing:
             self.exchange.begin_step()
         self.trace = []                                         # host enqueue order of compute segments and bucket hand-offs
         if self.use_graph:
-            if self._step_open and self._graph_no_fill:
-                # the previous replayed step was interrupted between two segments (an exception in a host collective, Ctrl-C): its
-                # partly accumulated gradients never reached the AdamW that re-zeroes them, and the graphs carry no fill of their own
+            if opening and self._step_open and self._graph_no_fill:
+                # the previous replayed step (accum_steps > 1: group) was interrupted between two segments (an exception in a host collective,
+                # Ctrl-C; between two micro-steps): its partly accumulated gradients never reached the AdamW that re-zeroes them, and the
+                # graphs carry no fill of their own
                 for st in self.stores:
                     st.grad.zero_()
             self._step_open = True
+            graphs = self.graphs if self.accum == 1 else self.graphs[kind]
             timed = self.exchange is not None and self.exchange.timing
             def run(coll, ev=None):
                 self._issue_event = ev
@@ -861,7 +1041,7 @@ class Trainer:
                     coll()
             host_issue = self.exchange_issue == 'host' and self.exchange is not None
             pending = None
-            for i, (g, coll) in enumerate(self.graphs):
+            for i, (g, coll) in enumerate(graphs):
                 self.trace.append(('seg', i))
                 g.replay()
                 if not host_issue:
@@ -879,25 +1059,24 @@ class Trainer:
                     run(*pending)
                     pending = None
                 if coll is not None:
-                    if i + 1 < len(self.graphs) and self.graphs[i + 1][1] is not None:
+                    if i + 1 < len(graphs) and graphs[i + 1][1] is not None:
                         pending = (coll, ev)
                     else:
                         run(coll, ev)
-            if timed:
+            if timed and closing:
                 self._host_comm_steps += 1
-            self._step_open = False
+            self._step_open = not closing                       # (an open group's sums wait for the closing micro-step's AdamW)
         else:
-            with self._wq_scope():
-                for i, (seg, coll) in enumerate(self._schedule()):
-                    self.trace.append(('seg', i))
-                    seg()
-                    if coll is not None:
-                        coll()
-        return self.loss_buf
+            self._run_eager(kind)
+        self._micro = (self._micro + 1) % self.accum
+        return self.loss_buf if self.accum == 1 or not self.use_graph else self._kind_loss[kind]
 
     def state_dict(self):
         """model + optimizer + RNG: what `accelerator.save_state` writes (train_caption.py:174; the reference itself only ever reloads
         the model weights, train_caption.py:103-108).  With shard_optimizer the Adam moments are this rank's slice."""
+        if self._micro:
+            raise RuntimeError(f'Trainer.state_dict() inside an open accumulation group (micro_index = {self._micro} of accum_steps = {self.accum}): '
+                               'the partial gradient sums are not part of a checkpoint; save at a group boundary (micro_index == 0)')
         return dict(it=self.it, m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
                     model={k: t.detach().clone() for k, t in self.model.state_dict().items()},      # (state_dict() aliases the live buffers)
                     seed=self.seed.clone(), rng=random.getstate(), world=self.world,
@@ -921,6 +1100,7 @@ class Trainer:
             dst.copy_(src)
         self.piece_state = {k: (m.to(self.device).clone(), v.to(self.device).clone()) for k, (m, v) in sd.get('pieces', {}).items()}
         self.it = int(sd['it'])
+        self.abort_group()                                      # resume at a group boundary (micro_index == 0)
         if 'seed' in sd:
             self.seed.copy_(sd['seed'])
         if 'rng' in sd:
