@@ -32,7 +32,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* ABI revision: bumped whenever an argument struct or a signature changes (101: ph_conv_gather window fields, ph_gemm_args row map +
  * defer_reduce; 102: round 4; 103: round 5 -- ph_ce_fwd takes a row_loss scratch, no memset nodes anywhere; 104: round 6 -- ph_dense_minmax_partial,
- * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
+ * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
 #define PH_VERSION 105
 
 enum { PH_OK = 0, PH_ERR_BAD_ARG = -1, PH_ERR_UNSUPPORTED = -2, PH_ERR_LAUNCH = -3 };
@@ -414,6 +414,44 @@ int ph_adamw(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, co
 int ph_adamw_keep(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
                   float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap,
                   hipStream_t stream);
+/* ---- device-side guard of the optimizer state: gradient-norm clipping and non-finite update skip ------------------------------------
+ * Stands for torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) (what accelerator.clip_grad_norm_ calls) in front of
+ * optimizer.step() in the reference loop (train_caption.py:126-135), and for the step GradScaler skips when a gradient holds inf / NaN
+ * (accelerate's scaler step under --mixed_precision fp16, train_caption.py:39): the decision is taken by kernels inside the captured
+ * step, the host never looks.  Three launches: ph_grad_sqnorm -> ph_clip_finalize -> ph_adamw_ctl (one per flat buffer).
+ *
+ * The control block (device memory, 8-byte aligned, owned by the caller; written by ph_clip_finalize only, with ordinary per-thread
+ * stores; `applied` / `skipped` are the only words it reads back, so the caller initialises those two). */
+typedef struct {
+  float coef;       /* what AdamW multiplies every gradient by on top of grad_scale: min(1, max_norm / (norm + 1e-6)), 1 without clipping */
+  int32_t apply;    /* 0: the update is skipped (skip_nonfinite and a non-finite sum of squares) */
+  float norm;       /* pre-clip total norm of the update gradient, fp32 */
+  int32_t finite;   /* the sum of squares, rounded to fp32, is finite */
+  double sumsq;     /* pre_scale^2 * sum of squares of the buffers, fp64 */
+  int64_t applied;  /* updates applied so far = Adam's t of the bias corrections */
+  int64_t skipped;  /* updates skipped so far */
+} ph_clip_ctl;
+#define PH_SQNORM_RANGES_MAX 4
+#define PH_SQNORM_BLOCKS_MAX 2048
+/* Streaming sum of squares of 1..PH_SQNORM_RANGES_MAX flat fp32 ranges (16-byte aligned, n[r] >= 1).  Range r is cut into
+ * blocks(n) = min(ceil(n / 8192), max(1, floor(PH_SQNORM_BLOCKS_MAX * n / sum_r n[r]))) contiguous chunks (the grid is shared out by length:
+ * every block of every range streams about the same number of bytes), one per block; every block writes ONE fp64 partial into
+ * `partials`, range after range (sum_r blocks(n[r]) doubles = ph_query_workspace(PH_WS_GRAD_NORM)).  Squares and sums are formed in fp64.
+ * No atomics, and the workspace needs no zeroing: every partial ph_clip_finalize reads was written by this launch. */
+int ph_grad_sqnorm(const float* const* ranges, const int64_t* n, int n_ranges, double* partials, int64_t partials_bytes, hipStream_t stream);
+/* One block: folds n_partials partials in a fixed order in fp64 (same buffer -> same bits on every replay), then
+ *   sumsq = pre_scale^2 * sum ; finite = (float)sumsq is finite ; norm = sqrt(sumsq), or inf / NaN when not finite (torch's fp32 norm)
+ *   coef  = max_norm < 0 ? 1 : min(1, max_norm / ((float)norm + 1e-6f))   (torch's coefficient and clamp; a NaN stays a NaN)
+ *   apply = !skip_nonfinite || finite ;  apply ? ++applied : ++skipped
+ *   hyper[1] = 1 - beta1^t, hyper[2] = 1 - beta2^t with t = max(applied, 1), evaluated in fp64, stored as fp32 (hyper[0], the learning
+ *   rate, stays the host's).  max_norm: > 0 (inf allowed) or < 0 for "no clipping"; 0 and NaN are PH_ERR_BAD_ARG. */
+int ph_clip_finalize(const double* partials, int n_partials, double pre_scale, float max_norm, int skip_nonfinite, double beta1,
+                     double beta2, float* hyper, ph_clip_ctl* ctl, hipStream_t stream);
+/* ph_adamw_keep under a control block: the gradient scale is grad_scale * ctl->coef, and with ctl->apply == 0 nothing is written
+ * but the gradient clean-up an applied launch would leave (zero_grad, keep bitmap, tail elements).  ctl == NULL: ph_adamw_keep, bit for bit. */
+int ph_adamw_ctl(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
+                 float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
+                 hipStream_t stream);
 int ph_cast_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t stream);
 int ph_cast_bf16_to_f32(const void* x, float* y, int64_t n, hipStream_t stream);
 /* y = bf16(x * scale): the gradient pack of the bf16 exchange payload, pre-scaled by 1/world BEFORE the rounding (round 3) */
@@ -466,8 +504,11 @@ int ph_gemm_dispatch_counts(int64_t* out, int n, int reset);
  *   PH_WS_CONV_COLSTATS   dims = {N}:       ph_gemm_args.col_stats ([PH_COLSTAT_SLABS][2][N] fp64, zeroed by the caller)
  *   PH_WS_BEAM_TOPK       dims = {B, nb, V}: ph_beam_topk_args.workspace, enough for nb_in = 1 and nb_in = nb:
  *                                            max(B * split(B, V), B*nb * split(B*nb, V)) records of 34 words, with
- *                                            split(rows, V) = max(ceil(V / 8192), min(16, ceil(512 / rows), ceil(V / 1024))) */
-enum { PH_WS_GEMM_SPLITK = 0, PH_WS_LAYERNORM_BWD = 1, PH_WS_ATTENTION_BWD = 2, PH_WS_CONV_COLSTATS = 3, PH_WS_BEAM_TOPK = 4 };
+ *                                            split(rows, V) = max(ceil(V / 8192), min(16, ceil(512 / rows), ceil(V / 1024)))
+ *   PH_WS_GRAD_NORM       dims = {n_0 [, n_1 ...]} (1 .. PH_SQNORM_RANGES_MAX range lengths): ph_grad_sqnorm's partials,
+ *                                            8 * sum_r min(ceil(n_r / 8192), max(1, floor(PH_SQNORM_BLOCKS_MAX * n_r / sum_q n_q))) bytes */
+enum { PH_WS_GEMM_SPLITK = 0, PH_WS_LAYERNORM_BWD = 1, PH_WS_ATTENTION_BWD = 2, PH_WS_CONV_COLSTATS = 3, PH_WS_BEAM_TOPK = 4,
+       PH_WS_GRAD_NORM = 5 };
 int64_t ph_query_workspace(int op, const int64_t* dims, int ndims);
 /* per-step host scalars written by a kernel whose ARGUMENTS carry them (no copy engine, no pinned staging): dst0[0..n0) and dst1[0..n1)
  * (32-bit words, device memory; dst1 may be NULL with n1 = 0) <- host_words[0..n0+n1), read before the call returns.  Replaces the two

@@ -150,6 +150,15 @@ class BeamAdvanceArgs(C.Structure):
 
 
 WS_BEAM_TOPK = 4         # PH_WS_BEAM_TOPK
+WS_GRAD_NORM = 5         # PH_WS_GRAD_NORM
+SQNORM_RANGES_MAX, SQNORM_BLOCKS_MAX = 4, 2048      # PH_SQNORM_RANGES_MAX, PH_SQNORM_BLOCKS_MAX
+
+
+class ClipCtl(C.Structure):
+    """ph_clip_ctl: 40 bytes of device memory; ops.clip_ctl() allocates it as five int64 words and hands out typed views"""
+    _fields_ = [('coef', c_float), ('apply', C.c_int32), ('norm', c_float), ('finite', C.c_int32), ('sumsq', C.c_double),
+                ('applied', c_i64), ('skipped', c_i64)]
+
 
 _SIGS = {
     'ph_version': (c_int, []),
@@ -192,6 +201,10 @@ _SIGS = {
                          c_float, c_float, c_int, c_void_p]),
     'ph_adamw_keep': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,
                               c_float, c_float, c_int, c_void_p, c_void_p]),
+    'ph_adamw_ctl': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,
+                             c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    'ph_grad_sqnorm': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
+    'ph_clip_finalize': (c_int, [c_void_p, c_int, C.c_double, c_float, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p]),
     'ph_cast_f32_to_bf16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
     'ph_cast_bf16_to_f32': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
     'ph_scale_cast_f32_to_bf16': (c_int, [c_void_p, c_void_p, c_i64, c_float, c_void_p]),

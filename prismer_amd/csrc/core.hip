@@ -22,6 +22,7 @@ extern "C" int ph_version(void) { return PH_VERSION; }
 
 extern "C" int ph_layernorm_bwd_blocks(int M);
 int64_t beam_topk_workspace_bytes(int64_t B, int64_t nb, int64_t V);     // beam.hip
+int64_t grad_norm_workspace_bytes(const int64_t* n, int n_ranges);       // optim.hip
 extern "C" int64_t ph_query_workspace(int op, const int64_t* dims, int ndims) {
   if (!dims) return -1;
   switch (op) {
@@ -42,6 +43,8 @@ extern "C" int64_t ph_query_workspace(int op, const int64_t* dims, int ndims) {
     case PH_WS_BEAM_TOPK:
       if (ndims != 3) return -1;
       return beam_topk_workspace_bytes(dims[0], dims[1], dims[2]);
+    case PH_WS_GRAD_NORM:
+      return grad_norm_workspace_bytes(dims, ndims);
     default:
       return -1;
   }

@@ -10,10 +10,28 @@ namespace {
 // torch.optim.AdamW:  p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ;
 //                     p -= (lr / bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 // HBM-bound: 16 B read + 14 B written per parameter.
+// CTL (ph_adamw_ctl): the control block ph_clip_finalize wrote in front of this launch scales the gradients once more (clip coefficient) or
+// turns the launch into its gradient clean-up alone (skipped update).  CTL = false is the kernel as it always was: no extra argument is read.
+template <bool CTL>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16* __restrict__ pb, int64_t n, const float* __restrict__ hyper,
                                                     float b1, float b2, float eps, float wd, float gscale, int zero_g, int mode,
-                                                    const uint32_t* __restrict__ keep) {
+                                                    const uint32_t* __restrict__ keep, const ph_clip_ctl* __restrict__ ctl) {
+  if (CTL) {
+    gscale *= ctl->coef;
+    if (!ctl->apply) {
+      // skipped update: p, m, v and the shadow keep their bits; the gradients are left as an applied launch leaves them (zero_grad except the
+      // kept chunks, tail elements included), so the next step starts from the same buffers either way
+      if (!zero_g) return;
+      const int64_t n4 = n >> 2;
+      for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const int64_t c = i >> 8;
+        if (!keep || !((keep[c >> 5] >> (c & 31)) & 1u)) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[(n4 << 2) + threadIdx.x] = 0.f;
+      return;
+    }
+  }
   const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2];
   const float step = lr / bc1, rbc2 = rsqrtf(bc2), decay = 1.f - lr * wd;
   int64_t n4 = n >> 2;
@@ -353,20 +371,37 @@ inline int grid_for(int64_t work_items) { return (int)std::min<int64_t>(ceil_div
 
 }  // namespace
 
-extern "C" int ph_adamw_keep(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
-                             float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap,
-                             hipStream_t stream) {
+static int adamw_launch(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2, float eps,
+                        float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl, hipStream_t stream) {
   PH_CHECK_ARG(p && g && m && v && hyper && n > 0, "ph_adamw: bad args");
+  // (30 B/parameter is what an APPLIED launch moves; the host cannot know the device's decision, so a skipped ph_adamw_ctl launch -- at most
+  // 4 B/parameter of zero stores, walked with a plain grid stride -- is booked the same: byte rates of the family are those of applied updates)
   ProfScope prof__(PH_FAM_OPTIM, 0.0, 30.0 * (double)n, stream);
   PH_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && (((uintptr_t)p_bf16) & 7) == 0, "ph_adamw: misaligned");
+  PH_CHECK_ARG((((uintptr_t)ctl) & 7) == 0, "ph_adamw_ctl: the control block must be 8-byte aligned");
   constexpr int mode = 1;             // contiguous chunk per block, two vectors per stream in flight (0: the round-1 one-vector grid-stride loop)
   constexpr int blocks_cap = 2048;    // 8 blocks per CU
   int grid = grid_for(n / 4 + 1);
   if (blocks_cap > 0 && grid > blocks_cap) grid = blocks_cap;
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps,
-                     weight_decay, grad_scale, zero_grad, mode, keep_bitmap);
+  if (ctl)
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps,
+                       weight_decay, grad_scale, zero_grad, mode, keep_bitmap, ctl);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps,
+                       weight_decay, grad_scale, zero_grad, mode, keep_bitmap, (const ph_clip_ctl*)nullptr);
   PH_LAUNCH_CHECK("adamw_kernel");
   return PH_OK;
+}
+extern "C" int ph_adamw_keep(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
+                             float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap,
+                             hipStream_t stream) {
+  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, nullptr, stream);
+}
+// the optimizer.step() of train_caption.py:133 behind clip_grad_norm_ / a scaler's skip: see include/prismer_hip.h
+extern "C" int ph_adamw_ctl(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
+                            float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
+                            hipStream_t stream) {
+  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, ctl, stream);
 }
 extern "C" int ph_adamw(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
                         float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, hipStream_t stream) {
@@ -648,6 +683,146 @@ extern "C" int ph_weighted_sum_f32(const float* x, const float* weights, int n, 
   ProfScope prof__(PH_FAM_MISC, 0.0, 0.0, stream, "ph_weighted_sum_f32");
   hipLaunchKernelGGL(weighted_sum_kernel, dim3(1), dim3(256), 0, stream, x, weights, n, scale, out);
   PH_LAUNCH_CHECK("weighted_sum_kernel");
+  return PH_OK;
+}
+// ---- gradient-norm clipping / non-finite update skip, decided on the device (include/prismer_hip.h: ph_clip_ctl) ---------------------
+// torch.nn.utils.clip_grad_norm_ (accelerator.clip_grad_norm_) in front of optimizer.step() of train_caption.py:126-135, and the step a
+// GradScaler skips (accelerate's scaler step, train_caption.py:39)
+namespace {
+// blocks of one range: its share of PH_SQNORM_BLOCKS_MAX (8 per CU) by LENGTH, so that every block of every range streams about the same number
+// of bytes and the grid drains together (a fixed count per range gave a 25 M and a 217 M range 1024 blocks each: the short blocks finished at
+// a ninth of the kernel and the long range streamed on with half the machine's blocks)
+inline int sqnorm_blocks(int64_t n, int64_t n_total) {
+  const int64_t share = std::max<int64_t>(1, (int64_t)PH_SQNORM_BLOCKS_MAX * n / n_total);
+  return (int)std::min<int64_t>(share, ceil_div64(n, 8192));
+}
+struct SqnormGroup {
+  int n;
+  int blk_start[PH_SQNORM_RANGES_MAX + 1];
+  const float* x[PH_SQNORM_RANGES_MAX];
+  int64_t len[PH_SQNORM_RANGES_MAX];
+};
+// HBM-bound: 4 B read per gradient.  Every block owns ONE contiguous chunk of its range (adamw_kernel's mode 1), eight 16-B loads per
+// thread in flight (what adamw_kernel keeps in flight over its four read streams), eight independent fp64 accumulators (conversion + fp64 FMA: two vector operations per 4 B, far under the load time; an fp32
+// accumulator would lose the low bits the 2x-vector_norm bar of the tests is made of, and overflow where fp64 reports the true sum).
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(SqnormGroup g, double* __restrict__ partials) {
+  __shared__ double red[4];
+  int r = 0;
+  while (r + 1 < g.n && (int)blockIdx.x >= g.blk_start[r + 1]) ++r;
+  const float* __restrict__ x = g.x[r];
+  const int64_t n = g.len[r], n4 = n >> 2;
+  const int nb = g.blk_start[r + 1] - g.blk_start[r], b = (int)blockIdx.x - g.blk_start[r];
+  constexpr int U = 8;
+  const int64_t per = ((n4 + nb - 1) / nb + 255) / 256 * 256;
+  const int64_t lo = (int64_t)b * per, hi = lo + per < n4 ? lo + per : n4;
+  double acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.0;
+  for (int64_t i0 = lo + threadIdx.x; i0 < hi; i0 += (int64_t)U * 256) {
+    f32x4 t[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = i0 + u * 256;
+      t[u] = i < hi ? reinterpret_cast<const f32x4*>(x)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const double a0 = t[u][0], a1 = t[u][1], a2 = t[u][2], a3 = t[u][3];
+      acc[u] = fma(a0, a0, acc[u]);
+      acc[u] = fma(a1, a1, acc[u]);
+      acc[u] = fma(a2, a2, acc[u]);
+      acc[u] = fma(a3, a3, acc[u]);
+    }
+  }
+  if (b == 0 && threadIdx.x < (n & 3)) { const double a = x[(n4 << 2) + threadIdx.x]; acc[0] = fma(a, a, acc[0]); }
+  double s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ partials, int np, double pre_scale, float max_norm,
+                                                            int skip_nonfinite, double b1, double b2, float* __restrict__ hyper,
+                                                            ph_clip_ctl* __restrict__ ctl) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < np; i += 256) s += partials[i];          // fixed order: thread, then the tree below
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const double sumsq = red[0] * pre_scale * pre_scale;
+  const int finite = isfinite((float)sumsq) ? 1 : 0;
+  // a sum of squares beyond fp32 reports what torch's fp32 norm of the same tensors reports: inf (NaN stays NaN)
+  const float normf = finite ? (float)sqrt(sumsq) : sqrtf((float)sumsq);
+  float coef = 1.f;
+  if (max_norm >= 0.f) {
+    coef = max_norm / (normf + 1e-6f);
+    if (coef > 1.f) coef = 1.f;                                            // torch.clamp(max=1.0): a NaN coefficient stays a NaN
+  }
+  const int apply = (!skip_nonfinite || finite) ? 1 : 0;
+  int64_t applied = ctl->applied, skipped = ctl->skipped;
+  if (apply) ++applied; else ++skipped;
+  const double t = (double)(applied > 0 ? applied : 1);
+  ctl->coef = coef; ctl->apply = apply; ctl->norm = normf; ctl->finite = finite; ctl->sumsq = sumsq;
+  ctl->applied = applied; ctl->skipped = skipped;
+  hyper[1] = (float)(1.0 - pow(b1, t));
+  hyper[2] = (float)(1.0 - pow(b2, t));
+}
+}  // namespace
+int64_t grad_norm_workspace_bytes(const int64_t* n, int n_ranges) {
+  if (!n || n_ranges < 1 || n_ranges > PH_SQNORM_RANGES_MAX) return -1;
+  int64_t blocks = 0, n_total = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    if (n[r] <= 0 || n[r] > (1ll << 40)) return -1;
+    n_total += n[r];
+  }
+  for (int r = 0; r < n_ranges; ++r) blocks += sqnorm_blocks(n[r], n_total);
+  return blocks * 8;
+}
+extern "C" int ph_grad_sqnorm(const float* const* ranges, const int64_t* n, int n_ranges, double* partials, int64_t partials_bytes, hipStream_t stream) {
+  PH_CHECK_ARG(ranges && n && partials && n_ranges >= 1 && n_ranges <= PH_SQNORM_RANGES_MAX, "ph_grad_sqnorm: need 1..%d ranges and a workspace, got %d",
+               PH_SQNORM_RANGES_MAX, n_ranges);
+  SqnormGroup g;
+  g.n = n_ranges;
+  int total = 0;
+  double bytes = 0.0;
+  int64_t n_total = 0;
+  for (int r = 0; r < n_ranges; ++r) {
+    PH_CHECK_ARG(ranges[r] && n[r] > 0 && n[r] <= (1ll << 40) && (((uintptr_t)ranges[r]) & 15) == 0,
+                 "ph_grad_sqnorm: range %d is null, empty, longer than 2^40 or not 16-byte aligned", r);
+    n_total += n[r];
+  }
+  for (int r = 0; r < n_ranges; ++r) {
+    g.x[r] = ranges[r]; g.len[r] = n[r];
+    g.blk_start[r] = total;
+    total += sqnorm_blocks(n[r], n_total);
+    bytes += 4.0 * (double)n[r];
+  }
+  for (int r = n_ranges; r < PH_SQNORM_RANGES_MAX; ++r) { g.x[r] = nullptr; g.len[r] = 0; g.blk_start[r + 1] = 0; }
+  g.blk_start[n_ranges] = total;
+  PH_CHECK_ARG((((uintptr_t)partials) & 7) == 0 && partials_bytes >= (int64_t)total * 8,
+               "ph_grad_sqnorm: workspace of %lld bytes, %lld needed (ph_query_workspace(PH_WS_GRAD_NORM))", (long long)partials_bytes, (long long)total * 8);
+  ProfScope prof__(PH_FAM_OPTIM, 0.0, bytes, stream, "ph_grad_sqnorm");
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(total), dim3(256), 0, stream, g, partials);
+  PH_LAUNCH_CHECK("grad_sqnorm_kernel");
+  return PH_OK;
+}
+extern "C" int ph_clip_finalize(const double* partials, int n_partials, double pre_scale, float max_norm, int skip_nonfinite, double beta1,
+                                double beta2, float* hyper, ph_clip_ctl* ctl, hipStream_t stream) {
+  PH_CHECK_ARG(partials && hyper && ctl && n_partials >= 1 && n_partials <= PH_SQNORM_BLOCKS_MAX + PH_SQNORM_RANGES_MAX,
+               "ph_clip_finalize: need partials, hyper, a control block and 1..%d partials (got %d)", PH_SQNORM_BLOCKS_MAX + PH_SQNORM_RANGES_MAX, n_partials);
+  PH_CHECK_ARG((((uintptr_t)partials | (uintptr_t)ctl) & 7) == 0, "ph_clip_finalize: partials and control block must be 8-byte aligned");
+  PH_CHECK_ARG(max_norm == max_norm && max_norm != 0.f, "ph_clip_finalize: max_norm must be > 0 (inf allowed) or < 0 for no clipping");
+  PH_CHECK_ARG(pre_scale == pre_scale && pre_scale > 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+               "ph_clip_finalize: need pre_scale > 0 and betas in [0, 1)");
+  ProfScope prof__(PH_FAM_OPTIM, 0.0, 8.0 * n_partials, stream, "ph_clip_finalize");
+  hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, stream, partials, n_partials, pre_scale, max_norm, skip_nonfinite, beta1, beta2, hyper, ctl);
+  PH_LAUNCH_CHECK("clip_finalize_kernel");
   return PH_OK;
 }
 extern "C" int ph_probe_layouts(const void* in_bf16, float* out, hipStream_t stream) {

@@ -787,6 +787,57 @@ def adamw(p, g, m, v, p_bf16, n, hyper, beta1=0.9, beta2=0.999, eps=1e-8, weight
                             weight_decay, grad_scale, int(zero_grad), ptr(keep), _stream()), 'ph_adamw')
 
 
+class ClipCtl:
+    """the device control block of the guarded update (ph_clip_ctl) and typed views of its words: coef / norm fp32 [1], apply / finite int32 [1],
+    sumsq fp64 [1], applied / skipped int64 [1].  Allocated zeroed: no update applied or skipped yet."""
+
+    def __init__(self, device):
+        self.words = torch.zeros(5, dtype=torch.int64, device=device)
+        f, i = self.words.view(F32), self.words.view(torch.int32)
+        self.coef, self.norm, self.apply, self.finite = f[0:1], f[2:3], i[1:2], i[3:4]
+        self.sumsq = self.words.view(torch.float64)[2:3]
+        self.applied, self.skipped = self.words[3:4], self.words[4:5]
+
+    def data_ptr(self):
+        return self.words.data_ptr()
+
+
+def grad_norm_workspace(lengths, device):
+    """the caller-owned partials of grad_sqnorm for ranges of these lengths (fp64, one per block), sized by ph_query_workspace"""
+    n = lib.ph_query_workspace(_lib.WS_GRAD_NORM, (C.c_int64 * len(lengths))(*lengths), len(lengths))
+    if n < 0:
+        raise _lib.PrismerHipError(f'ph_query_workspace(PH_WS_GRAD_NORM, {list(lengths)}): need 1..{_lib.SQNORM_RANGES_MAX} ranges of >= 1 element')
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+def grad_sqnorm(ranges, workspace=None):
+    """one fp64 partial sum of squares per block over the flat fp32 tensors `ranges` (ph_grad_sqnorm); returns the workspace, every element of
+    which this launch wrote.  Feed it to clip_finalize."""
+    assert all(t.dtype == F32 and t.is_contiguous() for t in ranges)
+    lengths = [t.numel() for t in ranges]
+    if workspace is None:
+        workspace = grad_norm_workspace(lengths, ranges[0].device)
+    k = len(ranges)
+    check(lib.ph_grad_sqnorm((C.c_void_p * k)(*[t.data_ptr() for t in ranges]), (C.c_int64 * k)(*lengths), k, workspace.data_ptr(),
+                             workspace.numel() * 8, _stream()), 'ph_grad_sqnorm')
+    return workspace
+
+
+def clip_finalize(partials, ctl, hyper, pre_scale=1.0, max_norm=None, skip_nonfinite=False, beta1=0.9, beta2=0.999):
+    """partials -> ctl (norm, clip coefficient, apply flag, applied / skipped counters) and Adam's bias corrections hyper[1:3] from the applied
+    count (ph_clip_finalize).  max_norm None: no clipping."""
+    assert partials.dtype == torch.float64 and hyper.dtype == F32 and hyper.numel() >= 3
+    check(lib.ph_clip_finalize(partials.data_ptr(), partials.numel(), float(pre_scale), -1.0 if max_norm is None else float(max_norm),
+                               int(bool(skip_nonfinite)), float(beta1), float(beta2), hyper.data_ptr(), ctl.data_ptr(), _stream()), 'ph_clip_finalize')
+
+
+def adamw_ctl(p, g, m, v, p_bf16, n, hyper, ctl, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.05, grad_scale=1.0, zero_grad=False, keep=None):
+    """adamw under a control block (ph_adamw_ctl): gradients scaled by grad_scale * ctl.coef; ctl.apply == 0 leaves p, m, v and the shadow alone"""
+    assert keep is None or keep.numel() * 32 * 1024 >= n
+    check(lib.ph_adamw_ctl(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), n, hyper.data_ptr(), beta1, beta2, eps,
+                           weight_decay, grad_scale, int(zero_grad), ptr(keep), ptr(ctl), _stream()), 'ph_adamw_ctl')
+
+
 def cast_to_bf16(x, out=None, scale=1.0):
     if out is None:
         out = torch.empty(x.shape, dtype=BF16, device=x.device)

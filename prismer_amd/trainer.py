@@ -54,13 +54,65 @@ def accum_plan(k, j, u=0, world=1):
                 seed_index=u * k + j, lr_index=u, bias_step=u + 1)
 
 
+def guarded_update_spec(grads, max_grad_norm=None, skip_nonfinite=False):
+    """The specification of Trainer(max_grad_norm=, skip_nonfinite=) as plain tensor code (tests/test_clip_cpu.py holds it against
+    torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW + a manual skip).  `grads`: the update gradient, tensor by tensor -- what AdamW would
+    consume, i.e. the flat buffers times Trainer._post_scale().  Returns (total_norm, coef, apply):
+      total_norm   ||g||_2 over all tensors, as clip_grad_norm_(params, max_norm, norm_type=2) forms it (norm of the per-tensor norms)
+      coef         what every gradient is multiplied by: min(1, max_grad_norm / (total_norm + 1e-6)) -- torch's coefficient and clamp, so a
+                   NaN norm gives a NaN coefficient and garbage propagates -- or 1 without max_grad_norm
+      apply        False only with skip_nonfinite and a non-finite sum of squares: the update is then not applied at all"""
+    norms = torch.stack([torch.linalg.vector_norm(g, 2) for g in grads])
+    total = torch.linalg.vector_norm(norms, 2)
+    coef = torch.ones_like(total) if max_grad_norm is None else torch.clamp(max_grad_norm / (total + 1e-6), max=1.0)
+    apply = (not skip_nonfinite) or bool(torch.isfinite(total * total))
+    return total, coef, apply
+
+
+def guarded_step_spec(params, grads, m, v, applied, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.05, max_grad_norm=None, skip_nonfinite=False):
+    """One guarded update in place on lists of tensors (torch.optim.AdamW's arithmetic, train_caption.py:111-112,133): the gradients are scaled by
+    guarded_update_spec's coefficient, and a skipped update touches neither params nor moments and does not move `applied`, Adam's t of the
+    bias corrections.  Returns (total_norm, apply, applied after the call).  The LR schedule position is the caller's: it counts iterations,
+    skipped ones included (cosine_lr_schedule(optimizer, i, ...) of the reference loop)."""
+    total, coef, apply = guarded_update_spec(grads, max_grad_norm, skip_nonfinite)
+    if not apply:
+        return total, False, applied
+    t = applied + 1
+    bc1, bc2 = 1.0 - betas[0] ** t, 1.0 - betas[1] ** t
+    for p, g, mm, vv in zip(params, grads, m, v):
+        g = g * coef
+        p.mul_(1.0 - lr * weight_decay)
+        mm.mul_(betas[0]).add_(g, alpha=1.0 - betas[0])
+        vv.mul_(betas[1]).addcmul_(g, g, value=1.0 - betas[1])
+        p.addcdiv_(mm, (vv.sqrt() / math.sqrt(bc2)).add_(eps), value=-lr / bc1)
+    return total, True, t
+
+
 class Trainer:
     def __init__(self, model, lr=5e-5, weight_decay=0.05, betas=(0.9, 0.999), eps=1e-8, min_lr=0.0, total_steps=1000,
                  task='caption', use_graph=True, process_group=None, bucket_mb=64, side_stream=False, micro_batches=1, keep_grads=False,
                  max_text_len=None, grad_payload='fp32', transport='torch.distributed', dec_backward_stages=3, lr_schedule=None,
                  shard_optimizer=False, overwrite_single_writer=True, allow_eager_fallback=False, broadcast_buffers=False, exchange_issue='device',
-                 accum_steps=1):
-        """accum_steps=k > 1: gradient accumulation.  k consecutive step() calls form one GROUP: each runs forward + backward on the bound
+                 accum_steps=1, max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm=c, skip_nonfinite=True: protection of the optimizer state, decided ON THE DEVICE inside the captured step (the host cannot: by
+        the time it could look at a loss the update has happened).  Specification: guarded_update_spec / guarded_step_spec above.  With g = the
+        update gradient (flat buffers x _post_scale(): the mean over ranks and over an accumulation group) and total_norm = ||g||_2 over the trainable
+        ranges of both stores, max_grad_norm=c makes AdamW see g * min(1, c / (total_norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_ in front of
+        optimizer.step() -- and skip_nonfinite=True drops an update whose sum of squares is not finite (rounded to fp32: what torch's fp32 norm
+        reports), the step a GradScaler skips in the reference's default fp16 run: master weights, both moments and the bf16 shadows keep their
+        bits, Adam's t (the count of APPLIED updates, kept on the device) does not move, the gradient buffers are cleaned exactly as an applied
+        update leaves them; `it` (the LR schedule position), the dropout seed, BatchNorm running statistics and the instance draws advance as
+        always.  BatchNorm running statistics polluted by a non-finite FORWARD are NOT rolled back (a NaN that enters through the stems poisons
+        them for good; one that enters through rgb reaches the ViT by the patch convolution only and touches none).  With skip_nonfinite=False a
+        non-finite norm behaves as torch's clip does: garbage propagates.  Read-outs: `grad_norm` (device tensor [1], pre-clip norm of the last
+        completed update), `applied_updates` / `skipped_updates` (host ints; reading them synchronises); state_dict() carries the applied count.
+        Cost: two launches per update in front of AdamW (a 4 B/parameter read + a one-block kernel), none with both options off -- that path is
+        the unguarded one, launch for launch.  accum_steps=k: only the closing micro-step measures, decides and updates (norm of the group's MEAN
+        gradient; a skipped group's sums are discarded like a consumed group's).  N ranks (plain all-reduce exchange, both payloads, both
+        exchange_issue modes): the norm is taken after the last range has been reduced, so every rank decides alike -- and the decoder's AdamW
+        therefore moves from beside the encoder backward to the optimizer tail.  Refused with shard_optimizer.
+
+        accum_steps=k > 1: gradient accumulation.  k consecutive step() calls form one GROUP: each runs forward + backward on the bound
         micro-batch (fixed size B, its own BatchNorm batch statistics, dropout masks and instance draws), the k-th also applies ONE AdamW update
         with the mean gradient of the group -- the reference loop (train_caption.py:126-135) written as
             cosine_lr_schedule(optimizer, u, ...); optimizer.zero_grad(); for j in 1..k: (model(b_j) / k).backward(); optimizer.step()
@@ -81,6 +133,16 @@ class Trainer:
         if self.accum > 1 and side_stream and micro_batches > 1:
             raise ValueError('accum_steps > 1 with the eager micro_batches experiment is not supported (micro_batches cuts ONE batch into parallel '
                              'branches; accum_steps is the gradient accumulation over several batches)')
+        if max_grad_norm is not None and not (float(max_grad_norm) > 0.0):             # (NaN fails the comparison too)
+            raise ValueError(f'max_grad_norm must be a positive number (inf allowed) or None, got {max_grad_norm!r}')
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guard = self.max_grad_norm is not None or self.skip_nonfinite
+        if self.guard and shard_optimizer:
+            raise ValueError('max_grad_norm / skip_nonfinite with shard_optimizer are not supported (every rank holds a slice of the update: the norm '
+                             'would need one more collective in front of the sharded tails)')
+        if self.guard and side_stream and micro_batches > 1:
+            raise ValueError('max_grad_norm / skip_nonfinite with the eager micro_batches experiment are not supported')
         self.model = model
         self.enc, self.dec = model.expert_encoder, model.text_decoder
         self.init_lr, self.min_lr, self.total_steps = lr, min_lr, total_steps
@@ -137,6 +199,10 @@ class Trainer:
         self.v = [torch.zeros(max(hi - lo, 1), dtype=F32, device=dev) for lo, hi in own]
         self.piece_state = {}                                  # rs_ag: (store index, a, b) -> (m, v)
         self.hyper = torch.zeros(3, dtype=F32, device=dev)
+        # guarded update: control block (clip coefficient, apply flag, norm, applied / skipped counters -- Adam's t lives THERE, the host writes
+        # hyper[0] only) and the per-block partials of the norm, both allocated once (nothing is allocated or zeroed inside the captured step)
+        self.ctl = ops.ClipCtl(dev) if self.guard else None
+        self._norm_ws = ops.grad_norm_workspace([st.n_train for st in self.stores if st.n_train], dev) if self.guard else None
         # accumulation group: [running sum of loss / k, this micro-step's loss / k, their sum] and the mean loss of the last COMPLETED group
         # (written by the closing micro-step only: the replays of the next group leave it alone)
         self._loss_acc = torch.zeros(3, dtype=F32, device=dev)
@@ -485,9 +551,34 @@ class Trainer:
 
     def _adamw(self, i):
         st = self.stores[i]
-        ops.adamw(st.master, st.grad, self.m[i], self.v[i], st.shadow, st.n_train, self.hyper, self.betas[0], self.betas[1], self.eps,
-                  self.wd, self._post_scale(), zero_grad=not self.keep_grads, keep=self._keep_maps[i] if self._keep_maps else None)
+        if self.guard:
+            ops.adamw_ctl(st.master, st.grad, self.m[i], self.v[i], st.shadow, st.n_train, self.hyper, self.ctl, self.betas[0], self.betas[1],
+                          self.eps, self.wd, self._post_scale(), zero_grad=not self.keep_grads, keep=self._keep_maps[i] if self._keep_maps else None)
+        else:
+            ops.adamw(st.master, st.grad, self.m[i], self.v[i], st.shadow, st.n_train, self.hyper, self.betas[0], self.betas[1], self.eps,
+                      self.wd, self._post_scale(), zero_grad=not self.keep_grads, keep=self._keep_maps[i] if self._keep_maps else None)
         st.refresh_derived()
+
+    def _measure_and_decide(self):
+        """guarded update, in front of the first AdamW launch (captured with it): sum of squares of both flat gradient buffers -> norm, clip
+        coefficient, apply flag, counters and bias corrections in the control block.  Two launches; every gradient is final here (one rank: the
+        whole backward ran; N ranks: the last range has been reduced), so every rank computes the same bits from the same reduced buffers."""
+        ops.grad_sqnorm([st.grad[:st.n_train] for st in self.stores if st.n_train], self._norm_ws)
+        ops.clip_finalize(self._norm_ws, self.ctl, self.hyper, self._post_scale(), self.max_grad_norm, self.skip_nonfinite, self.betas[0], self.betas[1])
+
+    @property
+    def grad_norm(self):
+        """device tensor [1]: pre-clip total norm of the update gradient of the last completed update (None with both options off)"""
+        return self.ctl.norm if self.guard else None
+
+    @property
+    def applied_updates(self):
+        """updates applied so far = Adam's t (host int; synchronises when an option is on, the count lives on the device)"""
+        return int(self.ctl.applied.item()) if self.guard else self.it
+
+    @property
+    def skipped_updates(self):
+        return int(self.ctl.skipped.item()) if self.guard else 0
 
     # ------------------------------------------------------------------------------------------ single-writer weight gradients
     @contextlib.contextmanager
@@ -586,6 +677,11 @@ class Trainer:
         """one rank: the decoder's gradients are final when the encoder backward starts, and nothing in the encoder backward
         reads a decoder weight -- its fused AdamW (HBM-bound: 5.1 GB of state for Prismer-BASE) runs as a parallel branch
         beside the MFMA-bound encoder backward instead of after it."""
+        if self.guard:
+            # the decision needs every gradient: both AdamW launches wait for the whole backward (_seg_optimizer_tail)
+            self._seg_enc_trunk_backward()
+            self._seg_enc_front_backward()
+            return
         main = torch.cuda.current_stream()
         if self.opt_stream is not None:
             ev = torch.cuda.Event()
@@ -605,7 +701,11 @@ class Trainer:
         ops.join_side()                                        # trunk gradients complete: their all-reduce may start
 
     def _seg_optimizer_tail(self):
-        """encoder AdamW (the decoder's already ran beside the encoder backward), dropout seed advance"""
+        """encoder AdamW (the decoder's already ran beside the encoder backward), dropout seed advance.  Guarded update: norm and decision,
+        then BOTH AdamW launches"""
+        if self.guard:
+            self._measure_and_decide()
+            self._adamw(1)
         self._adamw(0)
         ops.advance_seed(self.seed)
         self._grads_clean = not self.keep_grads
@@ -613,6 +713,8 @@ class Trainer:
     def _dec_adamw_after_comm(self):
         """N ranks: the decoder's AdamW starts on the optimizer stream as soon as its last bucket has been reduced and runs
         beside the encoder backward (an eager launch between graph replays, ordered by stream events like the collectives)"""
+        if self.guard:
+            return                                             # (the decoder's update waits for the norm over BOTH stores: _seg_optimizer_tail)
         self.opt_stream.wait_stream(self.comm_stream)
         with torch.cuda.stream(self.opt_stream):
             if self.shard:
@@ -739,7 +841,9 @@ class Trainer:
             return
         self.it += 1
         lr = self.lr_schedule(self.it - 1)
-        hyper = (lr, 1.0 - self.betas[0] ** self.it, 1.0 - self.betas[1] ** self.it)
+        # guarded update: the bias corrections follow the count of APPLIED updates, which only the device knows (ph_clip_finalize writes them)
+        # (getattr: tests/test_accum_logic_cpu.py drives this method on a stand-in object that predates the guard and has no such attribute)
+        hyper = (lr,) if getattr(self, 'guard', False) else (lr, 1.0 - self.betas[0] ** self.it, 1.0 - self.betas[1] ** self.it)
         if 'obj_detection' in self.enc.experts:
             ops.store_words(self.hyper, hyper, self.table, [random.randint(0, 127) for _ in range(256)])
         else:
@@ -870,7 +974,8 @@ class Trainer:
                     bufs=[b.clone() for mod in (self.enc, self.dec) for b in mod.buffers()], seed=self.seed.clone(), it=self.it,
                     rng=random.getstate(), grads=[st.grad.clone() for st in self.stores], clean=self._grads_clean,
                     pieces={k: (m.clone(), v.clone()) for k, (m, v) in self.piece_state.items()},
-                    micro=self._micro, step_open=self._step_open, loss_acc=self._loss_acc.clone(), group_loss=self._group_loss.clone())
+                    micro=self._micro, step_open=self._step_open, loss_acc=self._loss_acc.clone(), group_loss=self._group_loss.clone(),
+                    ctl=self.ctl.words.clone() if self.guard else None, hyper=self.hyper.clone())
 
     def _restore(self, snap):
         for st, t in zip(self.stores, snap['master']):
@@ -890,6 +995,8 @@ class Trainer:
         self.it, self._grads_clean = snap['it'], snap['clean']
         self._micro, self._step_open = snap['micro'], snap['step_open']
         self._loss_acc.copy_(snap['loss_acc']); self._group_loss.copy_(snap['group_loss'])
+        if self.guard:
+            self.ctl.words.copy_(snap['ctl']); self.hyper.copy_(snap['hyper'])
         random.setstate(snap['rng'])
 
     def _capture(self):
@@ -1077,7 +1184,7 @@ class Trainer:
         if self._micro:
             raise RuntimeError(f'Trainer.state_dict() inside an open accumulation group (micro_index = {self._micro} of accum_steps = {self.accum}): '
                                'the partial gradient sums are not part of a checkpoint; save at a group boundary (micro_index == 0)')
-        return dict(it=self.it, m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
+        return dict(it=self.it, applied=self.applied_updates, skipped=self.skipped_updates, m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
                     model={k: t.detach().clone() for k, t in self.model.state_dict().items()},      # (state_dict() aliases the live buffers)
                     seed=self.seed.clone(), rng=random.getstate(), world=self.world,
                     shard_optimizer='rs_ag' if self.rs_ag else self.shard,
@@ -1086,7 +1193,8 @@ class Trainer:
     def load_state_dict(self, sd, strict=True):
         """resume: masters (the module parameters are views of the flat buffers), bf16 shadows and derived conv shadows re-derived from
         them, Adam moments, iteration counter (LR schedule position), dropout seed and Python RNG (instance-embedding draws).  Captured
-        graphs stay valid: they reference the buffers, not their contents."""
+        graphs stay valid: they reference the buffers, not their contents.  The applied-update count (Adam's t) is restored into a guarded
+        Trainer; an unguarded one applies every update and keeps t = it."""
         mine = 'rs_ag' if self.rs_ag else self.shard
         if (sd.get("shard_optimizer", False) or False) != mine or ((self.shard or self.rs_ag) and sd.get("world", 1) != self.world):
             raise ValueError('Trainer.load_state_dict: optimizer sharding of the checkpoint '
@@ -1100,6 +1208,11 @@ class Trainer:
             dst.copy_(src)
         self.piece_state = {k: (m.to(self.device).clone(), v.to(self.device).clone()) for k, (m, v) in sd.get('pieces', {}).items()}
         self.it = int(sd['it'])
+        if self.guard:
+            # Adam's t: a checkpoint without the key (written before the guard existed, every update applied) loads with applied = it.  The
+            # skipped count is a diagnostic of this run and restarts from what the checkpoint says (0 when it says nothing).
+            applied = int(sd.get('applied', self.it))
+            self.ctl.applied.fill_(applied); self.ctl.skipped.fill_(int(sd.get('skipped', 0)))
         self.abort_group()                                      # resume at a group boundary (micro_index == 0)
         if 'seed' in sd:
             self.seed.copy_(sd['seed'])
