@@ -102,6 +102,11 @@ typedef struct {
    * else until the flush; a call that does not fit flushes first).  C is only valid after the flush.  One queue per process:
    * deferred calls and their flush must come from one thread and one stream. */
   int defer_reduce;
+  /* optional fp32 [M]: a_colsum[m] += sum_k A[k][m], the column sums of the A operand of a weight-gradient call (trans_a && trans_b, no conv
+   * gather) -- the bias gradient that goes with dW = dY^T X, taken from the dY fragments the GEMM already holds instead of a second pass
+   * over dY (same semantics as ph_colsum_bf16: exact bf16 values summed in fp32, added with float atomics).  Served by the grouped
+   * kernels: a single call that sets it is issued as a group of one. */
+  float* a_colsum;
 } ph_gemm_args;
 int ph_gemm_bf16(const ph_gemm_args* args, hipStream_t stream);
 /* launches the queued fold passes of the deferred split-K GEMMs (no-op when nothing is queued) */
@@ -114,6 +119,11 @@ int ph_gemm_flush_deferred(hipStream_t stream);
  * small GEMM per nn.Linear (dW = dY^T X, e.g. model/modules/roberta.py:79-183 has nine per decoder layer): their outputs
  * cover 18..144 tiles each, far fewer than the chip holds, so the host side defers them and issues each layer's set at once. */
 #define PH_GEMM_GROUP_MAX 16
+/* A [K,M] x [K,N] group with long reductions (every K a multiple of 64, >= 32 k-tiles) runs on a persistent grid of 256x128 tiles, one
+ * block per CU.  With a `workspace` shared by all its problems and plain fp32 outputs, the tiles of a problem may also be cut over K so
+ * that the units (problem, tile, k-range) of the whole group fill the 256 blocks evenly: every unit of a cut tile writes its fp32 tile
+ * to the workspace, and the unit that finishes last sums them in split order and writes C (accumulate / alpha as usual) -- inside the
+ * launch, no fold pass, bitwise reproducible.  Without a workspace, or one too small, the group runs whole.  ph_gemm_grouped_plan tells. */
 int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream);
 /* tuning hook for benchmarks and tests: variant of the big-tile (256x128, LDS-DMA) kernel -- 0 = off, 1 = plain main loop, 5 / 6 = ping-pong
  * main loop with the LEAN tail (no surplus DMA, no drain; round 4), 7 = 6 with the LDS-DMA requests spread over the M phase (round 6, default) -- and the
@@ -124,6 +134,11 @@ int ph_gemm_tuning(int big_mode, int big_min_tiles);
  * gradients issued beside the latency-bound backward chain of the decoder (roberta.py:212-231 in reverse) then fill the
  * idle CUs without taking every block slot from the chain's small kernels. */
 int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream);
+/* Host-only query: the plan ph_gemm_grouped_bf16 would use for this group on the persistent 256x128 weight-gradient kernel.  *units = work
+ * units (problem, tile, k-range) of the launch, *max_split = the largest number of k-ranges any problem's tiles are cut into (1 = no
+ * problem is split; partial sums of a split tile are folded inside the launch, in split order, by the unit that finishes last).
+ * Both are 0 when the group does not take that kernel.  Launches nothing. */
+int ph_gemm_grouped_plan(const ph_gemm_args* args, int n, int* units, int* max_split);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (fp32 math, eps inside the sqrt).  Replaces model/modules/utils.py:14-19 (F.layer_norm in

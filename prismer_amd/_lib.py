@@ -43,7 +43,8 @@ class GemmArgs(C.Structure):
                 ('out_f32', c_int), ('accumulate', c_int), ('alpha', c_float), ('split_k', c_int),
                 ('residual_f32', c_int), ('workspace', c_void_p), ('workspace_bytes', c_i64), ('pre_grad', c_int),
                 ('conv', C.POINTER(ConvGather)), ('col_stats', c_void_p),
-                ('rowmap_wo', c_int), ('rowmap_mul', c_int), ('rowmap_sub', c_int), ('rowmap_add', c_int), ('defer_reduce', c_int)]
+                ('rowmap_wo', c_int), ('rowmap_mul', c_int), ('rowmap_sub', c_int), ('rowmap_add', c_int), ('defer_reduce', c_int),
+                ('a_colsum', c_void_p)]
 
 
 class ConvDgradItem(C.Structure):
@@ -216,6 +217,7 @@ _SIGS = {
     'ph_conv_grad_from_shadow_grouped': (c_int, [c_void_p, c_int, c_void_p]),
     'ph_gemm_grouped_bf16': (c_int, [c_void_p, c_int, c_void_p]),
     'ph_gemm_grouped_capped_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    'ph_gemm_grouped_plan': (c_int, [c_void_p, c_int, C.POINTER(c_int), C.POINTER(c_int)]),
     'ph_gemm_tuning': (c_int, [c_int, c_int]),
     'ph_attention_tuning': (c_int, [c_int]),
     'ph_layernorm_tuning': (c_int, [c_int]),

@@ -40,7 +40,7 @@ void ph_prof_begin(int family, double flops, double bytes, hipStream_t s, const 
 void ph_prof_end(hipStream_t s);
 struct ProfScope {
   hipStream_t s; bool on;
-  ProfScope(int family, double flops, double bytes, hipStream_t st, const char* desc = nullptr) : s(st), on(g_ph_prof_enabled != 0) { if (on) ph_prof_begin(family, flops, bytes, st, desc); }
+  ProfScope(int family, double flops, double bytes, hipStream_t st, const char* desc = nullptr, bool enable = true) : s(st), on(enable && g_ph_prof_enabled != 0) { if (on) ph_prof_begin(family, flops, bytes, st, desc); }
   ~ProfScope() { if (on) ph_prof_end(s); }
 };
 

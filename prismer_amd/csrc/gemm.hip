@@ -21,6 +21,7 @@
 //   * split-K (grid.z): partial tiles to an fp32 workspace + splitk_reduce_kernel (which runs the same epilogue).
 //   * XCD-aware, grouped tile rasterisation (each XCD walks 8-row-panel groups, rows fastest).
 #include "gemm_common.h"
+#include <algorithm>
 #include <vector>
 
 using namespace phg;
@@ -193,6 +194,8 @@ static int fill_params(const ph_gemm_args* a, GemmParams& p) {
   p.act = a->act; p.out_f32 = a->out_f32; p.accumulate = a->accumulate; p.alpha = a->alpha; p.pre_grad = a->pre_grad;
   p.ws = nullptr; p.ldws = (a->N + 3) / 4 * 4;
   p.col_stats = a->col_stats;
+  PH_CHECK_ARG(!a->a_colsum || (a->trans_a && a->trans_b && !a->conv), "ph_gemm_bf16: a_colsum needs the [K][M] x [K][N] layout without a conv gather");
+  p.a_colsum = a->a_colsum; p.tile_cnt = nullptr;
   p.cv = ConvGather{};
   p.rm_wo = a->rowmap_wo; p.rm_mul = a->rowmap_mul; p.rm_sub = a->rowmap_sub; p.rm_add = a->rowmap_add;
   p.rm_inv_wo = a->rowmap_wo > 0 ? 1.0f / (float)a->rowmap_wo : 0.f;
@@ -222,11 +225,100 @@ static int fill_params(const ph_gemm_args* a, GemmParams& p) {
   return PH_OK;
 }
 
-extern "C" int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream) {
-  return ph_gemm_grouped_capped_bf16(args, n, 0, stream);
+// ---- plan of a weight-gradient group on the persistent 256x128 kernel ---------------------------------------------------------
+// The kernel's 256 blocks walk the units of the group in order, block b takes units b, b + 256, ...; a unit is (problem, tile, k-range).
+// Cost of a unit from the per-shape fits: 0.67 us per k-tile + 14 us fixed (prologue, parking, write-out); a unit of a tile
+// that is cut over K also writes its fp32 tile as a slab and one unit per tile reads them all back: + BIG_SLAB_US.  The makespan is the
+// longest block.  Unsplit, a group of T tiles costs ceil(T / 256) rounds whatever T % 256 is; cutting every tile of problem i into ns_i
+// k-ranges lets the units of the whole group fill the rounds evenly.
+// Floor: a unit shorter than BIG_FIXED_US / BIG_KTILE_US = 21 k-tiles spends more time in the fixed part than in its k loop, and every
+// further cut ADDS more fixed time to the chip than it removes loop time from the longest block -- no k-range is shorter than that.
+constexpr double BIG_KTILE_US = 0.67, BIG_FIXED_US = 14.0, BIG_SLAB_US = 6.0;
+constexpr int BIG_KT_FLOOR = 21;      // ceil(BIG_FIXED_US / BIG_KTILE_US)
+constexpr int BIG_MAX_SPLIT = 32, BIG_MAX_UNITS = 8192;
+static_assert(BIG_KT_FLOOR * BIG_KTILE_US >= BIG_FIXED_US && (BIG_KT_FLOOR - 1) * BIG_KTILE_US < BIG_FIXED_US, "floor = fixed part / k-tile time");
+struct BigPlan { int ns[PH_GEMM_GROUP_MAX]; int units, max_split; double cost; size_t ws_bytes; };
+
+static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* units_out) {
+  double load[256];
+  for (int b = 0; b < 256; ++b) load[b] = 0.0;
+  int u = 0;
+  for (int i = 0; i < n; ++i) {
+    const int tiles = ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN), kt = args[i].K / BK;
+    for (int sp = 0; sp < ns[i]; ++sp) {
+      const int len = kt / ns[i] + (sp < kt % ns[i] ? 1 : 0);
+      const double c = len * BIG_KTILE_US + BIG_FIXED_US + (ns[i] > 1 ? BIG_SLAB_US : 0.0);
+      for (int t = 0; t < tiles; ++t, ++u) load[u & 255] += c;
+    }
+  }
+  double worst = 0.0;
+  for (int b = 0; b < 256; ++b) worst = load[b] > worst ? load[b] : worst;
+  *units_out = u;
+  return worst;
+}
+// bytes of workspace a plan needs: per split problem one int counter per tile (256-B aligned block) + tiles x ns slabs of 256 x 128 fp32
+static size_t big_plan_ws(const ph_gemm_args* args, int n, const int* ns) {
+  size_t b = 0;
+  for (int i = 0; i < n; ++i) {
+    if (ns[i] <= 1) continue;
+    const size_t tiles = (size_t)ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
+    b += (tiles * 4 + 255) / 256 * 256 + tiles * ns[i] * (size_t)(big::BM * big::BN * 4);
+  }
+  return b;
+}
+static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split) {
+  BigPlan best;
+  int tiles_all = 0, kt_max = 0;
+  for (int i = 0; i < n; ++i) {
+    best.ns[i] = 1;
+    tiles_all += ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
+    kt_max = std::max(kt_max, args[i].K / BK);
+  }
+  best.max_split = 1; best.ws_bytes = 0;
+  best.cost = big_makespan(args, n, best.ns, &best.units);
+  // groups that fill whole rounds stay as they are
+  if (!may_split || tiles_all % 256 == 0) return best;
+  const ph_gemm_args& a0 = args[0];
+  // candidate c: k-ranges of about kt_max / c k-tiles for every problem of the group
+  for (int c = 2; c <= BIG_MAX_SPLIT && kt_max / c >= BIG_KT_FLOOR; ++c) {
+    BigPlan pl;
+    const double L = (double)kt_max / c;
+    pl.max_split = 1;
+    for (int i = 0; i < n; ++i) {
+      const int kt = args[i].K / BK;
+      pl.ns[i] = std::max(1, std::min({(int)lround(kt / L), kt / BIG_KT_FLOOR, BIG_MAX_SPLIT}));
+      pl.max_split = std::max(pl.max_split, pl.ns[i]);
+    }
+    pl.ws_bytes = big_plan_ws(args, n, pl.ns);
+    if (pl.ws_bytes > (size_t)a0.workspace_bytes) continue;
+    pl.cost = big_makespan(args, n, pl.ns, &pl.units);
+    if (pl.units <= BIG_MAX_UNITS && pl.cost < best.cost) best = pl;
+  }
+  return best;
 }
 
+// the arrival counters of a cut plan are zeroed by this kernel ahead of EVERY launch, on the launch's stream (a kernel, not a memset node:
+// small memset nodes replay wrongly inside a captured step on this ROCm, see tests/test_abi.py)
+__global__ void zero_counters_kernel(int* cnt, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) cnt[i] = 0;
+}
+
+static int gemm_grouped_impl(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream, bool plan_only, int* plan_units, int* plan_split);
+
+extern "C" int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream) {
+  return gemm_grouped_impl(args, n, 0, stream, false, nullptr, nullptr);
+}
 extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream) {
+  return gemm_grouped_impl(args, n, max_blocks, stream, false, nullptr, nullptr);
+}
+extern "C" int ph_gemm_grouped_plan(const ph_gemm_args* args, int n, int* units, int* max_split) {
+  PH_CHECK_ARG(units && max_split, "ph_gemm_grouped_plan: null output");
+  *units = 0; *max_split = 0;
+  return gemm_grouped_impl(args, n, 0, nullptr, true, units, max_split);
+}
+
+static int gemm_grouped_impl(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream, bool plan_only, int* plan_units, int* plan_split) {
   PH_CHECK_ARG(args && n >= 1 && n <= PH_GEMM_GROUP_MAX, "ph_gemm_grouped_bf16: need 1..%d problems, got %d", PH_GEMM_GROUP_MAX, n);
   double flops = 0.0, bytes = 0.0;
   double w128 = 0.0, w64 = 0.0, kt_max = 0.0;      // tile-iterations of work per tile shape
@@ -245,8 +337,8 @@ extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int 
     thin = thin || args[i].M <= 64 || args[i].N <= 64;
   }
   char desc__[96];
-  if (g_ph_prof_enabled) snprintf(desc__, sizeof(desc__), "gemm grouped n=%d ta=%d tb=%d K0=%d", n, args[0].trans_a, args[0].trans_b, args[0].K);
-  ProfScope prof__(PH_FAM_GEMM, flops, bytes, stream, desc__);
+  if (g_ph_prof_enabled && !plan_only) snprintf(desc__, sizeof(desc__), "gemm grouped n=%d ta=%d tb=%d K0=%d", n, args[0].trans_a, args[0].trans_b, args[0].K);
+  ProfScope prof__(PH_FAM_GEMM, flops, bytes, stream, desc__, !plan_only);
   // 128x128 tiles (twice the arithmetic intensity per staged byte) unless the group is so small that they would leave most
   // CUs idle; long reductions always take them (measured: 16 adaptor wgrads 768x384xK=8320 ran 440 us on 64x64 tiles)
   double t128 = 0.0;
@@ -266,6 +358,71 @@ extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int 
     total += g.p[i].tiles_m * g.p[i].tiles_n;
   }
   g.tile_start[n] = total;
+  // ---- weight-gradient groups with long reductions: the 256x128 ping-pong kernel, one persistent block per CU, units = (tile, k-range) ----
+  BigPlan plan;
+  bool use_big = false, big_first = false;
+  {
+    bool ok = big_mode_now() > 0 && !conv && max_blocks == 0 && args[0].trans_a && args[0].trans_b;
+    // the tiles may be cut over K when the caller hands every problem the same workspace and the write-out is the plain fp32 one
+    bool may_split = args[0].workspace && args[0].workspace_bytes > 0;
+    bool roomy = true;            // every problem covers at least one whole 256x128 tile
+    int kt_min = 1 << 30, kt_big = 0;
+    for (int i = 0; i < n && ok; ++i) {
+      const ph_gemm_args& a = args[i];
+      ok = (a.K % BK) == 0 && (a.M % 8) == 0 && (a.N % 8) == 0 && a.M >= 8 && a.N >= 8 && !a.col_stats;
+      may_split = may_split && a.workspace == args[0].workspace && a.out_f32 && !a.bias && a.act == PH_ACT_NONE && !a.pre_out && !a.act_in &&
+                  !a.residual && !(a.drop_p > 0.f) && a.rowmap_wo == 0;
+      roomy = roomy && a.M >= big::BM && a.N >= big::BN;
+      kt_min = min(kt_min, a.K / BK); kt_big = max(kt_big, a.K / BK);
+    }
+    if (ok && kt_min >= 32) {
+      // makespan of the persistent kernel under its best plan (plan_big_wgrad) against rounds x (k loop + fixed part) of the 128x128 grouped
+      // kernel: 0.84 us per k-tile and pair of co-resident 128x128 blocks (0.5 us for a lone one)
+      plan = plan_big_wgrad(args, n, may_split);
+      const int t128 = total;           // (tiles of the BMsel grid computed above; BMsel is 128 for these groups)
+      const double cost_128 = BMsel == 128 ? (t128 <= 256 ? kt_big * 0.5 + 10.0 : ceil(t128 / 512.0) * (kt_big * 0.84 + 10.0)) : 1e30;
+      use_big = plan.cost < cost_128;
+      // a cut plan over whole tiles goes ahead of the register-staged split below (which is for outputs far smaller than a 256x128 tile:
+      // the stems' 96 x 32 weight gradients)
+      big_first = use_big && plan.max_split > 1 && roomy;
+    }
+  }
+  auto launch_big = [&]() -> int {
+    if (plan_only) { *plan_units = plan.units; *plan_split = plan.max_split; return PH_OK; }
+    int tot = 0;
+    size_t off = 0;
+    char* const ws = reinterpret_cast<char*>(args[0].workspace);
+    for (int i = 0; i < n; ++i) {
+      const int tiles = ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
+      g.p[i].tiles_m = ceil_div(args[i].M, big::BM); g.p[i].tiles_n = ceil_div(args[i].N, big::BN);
+      g.p[i].k_tiles_per_split = ceil_div(args[i].K / BK, plan.ns[i]);
+      g.p[i].ws = nullptr; g.p[i].tile_cnt = nullptr;
+      g.nsplit[i] = plan.ns[i];
+      if (plan.ns[i] > 1) {
+        // counters of all split problems first (zeroed by one small kernel), slabs behind them
+        g.p[i].tile_cnt = reinterpret_cast<int*>(ws + off);
+        off += ((size_t)tiles * 4 + 255) / 256 * 256;
+      }
+      g.tile_start[i] = tot;
+      tot += tiles * plan.ns[i];
+    }
+    g.tile_start[n] = tot;
+    if (off > 0) {
+      // zeroed on the stream ahead of EVERY launch (captured with the step): the counters of an earlier launch -- or of a launch that never
+      // finished, or whatever the workspace held before -- are never trusted
+      const int words = (int)(off / 4);
+      hipLaunchKernelGGL(zero_counters_kernel, dim3(ceil_div(words, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(ws), words);
+      PH_LAUNCH_CHECK("zero_counters_kernel");
+      for (int i = 0; i < n; ++i) {
+        if (plan.ns[i] <= 1) continue;
+        const size_t tiles = (size_t)g.p[i].tiles_m * g.p[i].tiles_n;
+        g.p[i].ws = reinterpret_cast<float*>(ws + off);
+        off += tiles * plan.ns[i] * (size_t)(big::BM * big::BN * 4);
+      }
+    }
+    return big::launch_grouped_wgrad(g, tot, big_mode_now() >= 7 ? 7 : 5, stream);
+  };
+  if (big_first) return launch_big();
   // ---- grouped AND split over K (round 3): weight-gradient groups with few output tiles and very long reductions -- the stems' conv
   // weight gradients, 6 experts x (2..42 tiles over up to 6272 k-tiles).  As single launches each of them split K on its own (28-92 us
   // per launch at 5-60 % fill, 28 launches per step); here every problem is cut into pieces of ~W/slots k-tiles so that the whole
@@ -296,6 +453,7 @@ extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int 
         blocks += g.p[i].tiles_m * g.p[i].tiles_n * ns;
       }
       if (any && off <= (size_t)a0.workspace_bytes) {
+        if (plan_only) return PH_OK;
         int tot = 0;
         for (int i = 0; i < n; ++i) {
           const int kti = ceil_div(args[i].K, BK);
@@ -325,35 +483,8 @@ extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int 
       }
     }
   }
-  // ---- weight-gradient groups with long reductions: the 256x128 ping-pong kernel, one persistent block per CU ----
-  {
-    bool ok = big_mode_now() > 0 && !conv && max_blocks == 0 && args[0].trans_a && args[0].trans_b;
-    int tbig = 0, kt_min = 1 << 30, kt_big = 0;
-    for (int i = 0; i < n && ok; ++i) {
-      const ph_gemm_args& a = args[i];
-      ok = (a.K % BK) == 0 && (a.M % 8) == 0 && (a.N % 8) == 0 && a.M >= 8 && a.N >= 8 && !a.col_stats;
-      tbig += ceil_div(a.M, big::BM) * ceil_div(a.N, big::BN);
-      kt_min = min(kt_min, a.K / BK); kt_big = max(kt_big, a.K / BK);
-    }
-    if (ok && kt_min >= 32) {
-      // rounds x (k loop + fixed part) of either kernel, constants from the per-shape fits: 0.67 us per k-tile for the
-      // one-per-CU 256x128 block, 0.84 us per k-tile and pair of co-resident 128x128 blocks (0.5 us for a lone one)
-      const double cost_big = ceil(tbig / 256.0) * (kt_big * 0.67 + 14.0);
-      const int t128 = total;           // (tiles of the BMsel grid computed above; BMsel is 128 for these groups)
-      const double cost_128 = BMsel == 128 ? (t128 <= 256 ? kt_big * 0.5 + 10.0 : ceil(t128 / 512.0) * (kt_big * 0.84 + 10.0)) : 1e30;
-      if (cost_big < cost_128) {
-        int tot = 0;
-        for (int i = 0; i < n; ++i) {
-          g.p[i].tiles_m = ceil_div(args[i].M, big::BM); g.p[i].tiles_n = ceil_div(args[i].N, big::BN);
-          g.p[i].k_tiles_per_split = args[i].K / BK;
-          g.tile_start[i] = tot;
-          tot += g.p[i].tiles_m * g.p[i].tiles_n;
-        }
-        g.tile_start[n] = tot;
-        return big::launch_grouped_wgrad(g, tot, big_mode_now() >= 7 ? 7 : 5, stream);
-      }
-    }
-  }
+  if (use_big) return launch_big();
+  if (plan_only) return PH_OK;
   const int ta = args[0].trans_a, tb = args[0].trans_b;
   // ---- forward-shaped implicit convolutions with many rows and a long reduction (the stems' layers 2..4 and their data gradients): the
   // 256x128 LDS-DMA kernel with the gather in the DMA source address (round 4; the register-staged gather kernel ran them at ~410 TFLOP/s)
@@ -427,6 +558,7 @@ extern "C" int ph_gemm_bf16(const ph_gemm_args* a, hipStream_t stream) {
   if (g_ph_prof_enabled) snprintf(desc__, sizeof(desc__), "gemm M=%d N=%d K=%d ta=%d tb=%d f32=%d acc=%d", a->M, a->N, a->K, a->trans_a, a->trans_b, a->out_f32, a->accumulate);
   ProfScope prof__(PH_FAM_GEMM, 2.0 * a->M * (double)a->N * a->K, 2.0 * ((double)a->M * a->K + (double)a->N * a->K + (double)a->M * a->N), stream, desc__);
   if (a->conv && !a->trans_a && !a->trans_b) return ph_gemm_grouped_capped_bf16(a, 1, 0, stream);     // implicit-GEMM forward: grouped kernel
+  if (a->a_colsum) return ph_gemm_grouped_capped_bf16(a, 1, 0, stream);                               // fused column sums: grouped kernels
   GemmParams p;
   {
     int rc = fill_params(a, p);

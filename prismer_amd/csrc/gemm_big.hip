@@ -30,9 +30,15 @@ typedef __attribute__((address_space(3))) void lptr_t;
 // (element offset of tap (0,0) + a bit mask of the taps inside the image); a chunk that falls outside the image, or beyond the real K, reads
 // the library's ZERO PAGE instead (p.zero16).  K need not be a multiple
 // of 64 here (K = 9 * 96 = 864): the chunks of B beyond K read the zero page as well.
-template <int VARIANT, bool TA, bool TB, bool XCD_REMAP, int CONV = 0>
-__device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id) {
+// WG = true (persistent weight-gradient kernel, gemm_big_grouped_kernel): the unit of work is (tile, k-range) -- the unit multiplies the nk_unit
+// k-tiles from kt0 on and is number `split` of the `nsplit` units of its tile.  nsplit > 1: the parked fp32 tile goes to the workspace as a slab,
+// and the unit that arrives LAST at the tile's counter sums the slabs in split order and runs the write-out (nobody waits for anybody: a
+// unit that is not last simply returns).  p.a_colsum: units of the tn == 0 column also sum the A fragments they hold over their k range.
+template <int VARIANT, bool TA, bool TB, bool XCD_REMAP, int CONV = 0, bool WG = false>
+__device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id, const int kt0 = 0, const int nk_unit = 0, const int split = 0,
+                                         const int nsplit = 1) {
   static_assert(CONV == 0 || (CONV == 1 && !TA && !TB && (VARIANT & 4)), "conv gather: A of a forward-shaped problem, ping-pong loop");
+  static_assert(!WG || (TA && TB && CONV == 0 && !XCD_REMAP && (VARIANT & 12) == 12), "k-range units: weight-gradient layout, ping-pong loop, LEAN tail");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // tile mapping.  Hardware places block b on XCD b % 8, each XCD with its own 4-MB L2.  One-tile-per-block launches (XCD_REMAP) give every
   // XCD WHOLE row panels: XCD x owns tiles_m / 8 (+1) consecutive 256-row panels with ALL their column tiles, so an A panel is fetched
@@ -72,7 +78,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
     tm = first_m + rin % gm; tn = rin / gm;
   }
   const int m0 = tm * BM, n0 = tn * BN;
-  const int nk = CONV ? (p.K + BK - 1) / BK : p.K / BK;
+  const int nk = WG ? nk_unit : (CONV ? (p.K + BK - 1) / BK : p.K / BK);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -106,7 +112,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
     } else if constexpr (TA) {   // A = [K][M]: one instruction = 2 k-rows x 512 B; lane -> k-row (lane >> 5), LDS slot lane & 31 holds chunk c
       const int kr = (i * 8 + wave) * 2 + (lane >> 5), pos = lane & 31;
       const int c = (((pos >> 2) ^ (kr & 3)) << 2) | (pos & 3);
-      a_src[i] = p.A + (size_t)kr * p.lda + min(m0 + c * 8, p.M - 8);
+      a_src[i] = p.A + (size_t)(kr + (WG ? kt0 * BK : 0)) * p.lda + min(m0 + c * 8, p.M - 8);
     } else {
       const int r = (i * 8 + wave) * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((r >> 1) & 7);
@@ -118,7 +124,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
     if constexpr (TB) {   // B = [K][N]: one instruction = 4 k-rows x 256 B; lane -> k-row (lane >> 4), LDS slot lane & 15 holds chunk c
       const int kr = (i * 8 + wave) * 4 + (lane >> 4), pos = lane & 15;
       const int c = (((pos >> 2) ^ (kr & 3)) << 2) | (pos & 3);
-      b_src[i] = p.B + (size_t)kr * p.ldb + min(n0 + c * 8, p.N - 8);
+      b_src[i] = p.B + (size_t)(kr + (WG ? kt0 * BK : 0)) * p.ldb + min(n0 + c * 8, p.N - 8);
     } else {
       const int r = (i * 8 + wave) * 8 + (lane >> 3);
       const int c = (lane & 7) ^ ((r >> 1) & 7);
@@ -216,6 +222,16 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+  // Column sums of A (p.a_colsum, units with tn == 0): one more MFMA per A fragment against a fragment of ones -- the products are the exact
+  // bf16 values, summed in fp32; every accumulator element of lane l then holds the sum for fragment row (l & 31).  The two waves of a wave row
+  // hold the same two A fragments and share the duty: wave wn takes fragment wn (one accumulator, 16 registers).  The MFMAs go into the M phase, whose
+  // length is set by the partner wave's fragment reads (the loop is LDS bound), not into the R phase, where VALU conversions and adds would
+  // lengthen the bound itself; nothing is added at the head of the phase.
+  const bool do_cs = WG && p.a_colsum != nullptr && tn == 0;
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
+  f32x16 cs = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool cs0 = do_cs && wn == 0, cs1 = do_cs && wn == 1;
 
   auto compute = [&](int stage) {
     const char* la = smem + stage * STAGE;
@@ -344,6 +360,10 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
             if (mine) issue_piece(kt_n, sn, std::integral_constant<int, m / 2>{});
             __builtin_amdgcn_sched_barrier(0);
           }
+          if constexpr (WG && (m & 3) == 3) {          // behind the last MFMA of a 16-k slice
+            if (cs0) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[kk][0], cs, 0, 0, 0);
+            if (cs1) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[kk][1], cs, 0, 0, 0);
+          }
         });
       } else {
       if constexpr (ISS0 && ISS1) issue(min(t + 2 + grp, nk - 1), sn);
@@ -354,6 +374,13 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[kk][j], fx[kk][i], acc[i][j], 0, 0, 0);
+      if constexpr (WG) {
+#pragma unroll
+        for (int kk = 0; kk < BK / 16; ++kk) {
+          if (cs0) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[kk][0], cs, 0, 0, 0);
+          if (cs1) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[kk][1], cs, 0, 0, 0);
+        }
+      }
       }
       if (VARIANT & 1) __builtin_amdgcn_s_setprio(0);
       if (!grp) {
@@ -391,7 +418,8 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   // loop never waits on memory (gemm_common.h, "Round 4").  Raw s_barrier + lgkmcnt(0): __syncthreads() would drain those loads.
   const int epi = epi_classify(p, false);
   PH_WO_DECL(BM, BN, NTHR);
-  wo_prefetch<BM, BN, NTHR>(epi, p, m0, n0, PH_WO_ARGS);
+  const bool slab = WG && nsplit > 1;
+  if (!slab) wo_prefetch<BM, BN, NTHR>(epi, p, m0, n0, PH_WO_ARGS);
   DropCtx dc;
   const bool drop = p.drop_p > 0.0f;
   if (drop) dc = make_drop(p.drop_seed, p.drop_stream, p.drop_p);
@@ -405,10 +433,64 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
                acc[i][j][g * 4 + 3] * p.alpha};
     *reinterpret_cast<f32x4*>(cl + ml * BN + ((c ^ (ml & (CH - 1))) << 2)) = v;
   });
+  // (WG) the 16 KB of the ring behind the parked tile: [0] the "this unit arrived last" flag, from byte 64 on the column sums csl[256]
+  int* const last_flag = reinterpret_cast<int*>(smem + BM * BN * 4);
+  float* const csl = reinterpret_cast<float*>(smem + BM * BN * 4 + 64);
+  if constexpr (WG) {
+    if (do_cs && lane < 32) csl[wm * 64 + wn * 32 + lane] = cs[0];
+  }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
   PH_TL(5);
+  if constexpr (WG) {
+    // one float atomic per column and unit: waves 0..3 add 64 consecutive columns each (256 contiguous bytes per wave instruction)
+    if (do_cs && threadIdx.x < BM && m0 + (int)threadIdx.x < p.M) atomicAdd(p.a_colsum + m0 + threadIdx.x, csl[threadIdx.x]);
+    if (slab) {
+      constexpr int TILE = BM * BN, VEC = TILE / 4 / NTHR;               // 16 16-B vectors per thread
+      float* const tile_ws = p.ws + (size_t)block_id * nsplit * TILE;
+      float* const mine = tile_ws + (size_t)split * TILE;
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const int o = (i * NTHR + (int)threadIdx.x) * 4;
+        *reinterpret_cast<f32x4*>(mine + o) = *reinterpret_cast<const f32x4*>(cl + o);
+      }
+      // publish: every wave's slab stores are complete, then ONE agent-scope release and the ticket; the unit that draws the last ticket
+      // acquires once.  No unit ever waits for another one: any arrival order is correct.
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const int ticket = __hip_atomic_fetch_add(p.tile_cnt + block_id, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = ticket == nsplit - 1 ? 1 : 0;
+        if (last) {
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        *last_flag = last;
+      }
+      __syncthreads();
+      if (*last_flag == 0) return;
+      // fold: the slabs in split order (this unit's own included, from memory: a fixed order whoever arrives last), each thread the 16
+      // vectors it parked itself -- all loads of a slab are requested before the first add
+      wo_prefetch<BM, BN, NTHR>(epi, p, m0, n0, PH_WO_ARGS);
+      f32x4 sum[VEC];
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) sum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int sp = 0; sp < nsplit; ++sp) {
+        const float* src = tile_ws + (size_t)sp * TILE;
+        f32x4 v[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = *reinterpret_cast<const f32x4*>(src + (i * NTHR + (int)threadIdx.x) * 4);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) sum[i] += v[i];
+      }
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) *reinterpret_cast<f32x4*>(cl + (i * NTHR + (int)threadIdx.x) * 4) = sum[i];
+      __syncthreads();
+    }
+  }
   tile_writeout<BM, BN, NTHR>(PH_TL_ARG epi, p, cl, m0, n0, false, drop, dc, PH_WO_ARGS);
   if constexpr (CONV == 1) {
     if (p.col_stats) tile_colstats<BM, BN, NTHR>(p, cl, m0, n0);       // train-mode BatchNorm sums from the parked tile
@@ -451,7 +533,11 @@ __global__ __launch_bounds__(NTHR) void gemm_big_grouped_kernel(GroupParams g) {
     const int q = cnt / 8, r = cnt % 8, xcd = blockIdx.x % 8, idx = blockIdx.x / 8;
     const int t = base + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     while (i + 1 < g.n && t >= g.tile_start[i + 1]) ++i;
-    big_tile<VARIANT, TA, TB, false>(g.p[i], t - g.tile_start[i]);
+    // unit -> (tile, k-range): tiles fastest (units that run side by side share operand panels of one k-range), the k-tiles of a tile cut
+    // into nsplit ranges that differ by at most one k-tile
+    const int local = t - g.tile_start[i], ns = g.nsplit[i], ntile = g.p[i].tiles_m * g.p[i].tiles_n;
+    const int sp = local / ntile, kt = g.p[i].K / BK, kq = kt / ns, kr = kt - kq * ns;
+    big_tile<VARIANT, TA, TB, false, 0, true>(g.p[i], local - sp * ntile, sp * kq + min(sp, kr), kq + (sp < kr ? 1 : 0), sp, ns);
     __syncthreads();                     // the write-out's LDS staging area is the next tile's DMA ring
   }
 }

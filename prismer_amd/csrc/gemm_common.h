@@ -63,6 +63,9 @@ struct GemmParams {
   double* col_stats;       // optional fp64 [2][N]: += column sums / sums of squares of the (bf16-rounded) outputs (BatchNorm statistics)
   int rm_wo, rm_mul, rm_sub, rm_add; float rm_inv_wo;     // output row map (rm_wo > 0): C row of result row m = m * mul - (m % wo) * sub + add
   ConvGather cv;           // CONV kernels only: geometry of the gathered operand (A for CONV=1, B for CONV=2)
+  float* a_colsum;         // optional fp32 [M] (A = [K][M], B = [K][N] kernels): += column sums of A over the k range of every unit with tn == 0
+  int* tile_cnt;           // persistent 256x128 weight-gradient kernel, problem cut over K: one arrival counter per tile (zeroed ahead of the launch);
+                           // ws then holds the fp32 slabs ws[tile][split][256 * 128] of the tile's units
   const bf16* zero16;      // >= 1 KB of device-resident zeros (64 lanes x 16 B): what the LDS-DMA lanes read for a padding tap / a chunk beyond K (gemm_big.hip, CONV)
 };
 
@@ -686,6 +689,7 @@ struct GroupParams {
   int n;
   int tile_start[PH_GEMM_GROUP_MAX + 1];   // first block of problem i (blocks of a problem = tiles x nsplit)
   int nsplit[PH_GEMM_GROUP_MAX];           // k splits of problem i (1 = none): block b of the problem is tile b % tiles, split b / tiles
+                                           // (256x128 persistent kernel: split s covers k-tiles s*q + min(s, r) .. with q = kt / nsplit, r = kt % nsplit)
   GemmParams p[PH_GEMM_GROUP_MAX];
 };
 

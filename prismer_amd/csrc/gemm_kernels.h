@@ -94,6 +94,20 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int block_i
     if constexpr (CONV == 2) store_ks_conv<BN>(sb, xb);
     else if (TB) store_ks<BN>(sb, xb, tid); else store_kc<BN>(sb, xb, tid);
   };
+  // Column sums of A (p.a_colsum; [K][M] x [K][N] problems, tiles with tn == 0): one more MFMA per A fragment against a fragment of ones --
+  // exact bf16 values summed in fp32, every accumulator element of lane l = the sum for fragment row (l & 31).  The two waves of a wave row
+  // hold the same fragments and share the duty with ONE accumulator each (16 registers: the 128x128 kernels run at the edge of their 256-register
+  // budget): with two fragments per wave (TM = 2) wave wn takes fragment wn, with one it takes the 16-k slices with (kk & 1) == wn.
+  // Rows past K are zero in the staged image (K tail).
+  constexpr bool CS = TA && TB && CONV == 0 && KS == 1;
+  static_assert(!CS || TM <= 2, "column sums: one or two A fragments per wave");
+  bool cs0 = false, cs1 = false;                    // this wave is the wn = 0 / wn = 1 wave of a tile that sums
+  const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
+  f32x16 cs = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if constexpr (CS) {
+    const bool do_cs = p.a_colsum != nullptr && tn == 0;
+    cs0 = do_cs && wn == 0; cs1 = do_cs && wn == 1;
+  }
   auto compute = [&](int buf) {
     const char* la = smem_g + buf * STAGE;
     const char* lb = la + A_BYTES;
@@ -111,6 +125,12 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int block_i
 #pragma unroll
         for (int j = 0; j < TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[j], fx[i], acc[i][j], 0, 0, 0);
+      if constexpr (CS && TM == 2) {
+        if (cs0) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[0], cs, 0, 0, 0);
+        if (cs1) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[TM - 1], cs, 0, 0, 0);
+      } else if constexpr (CS) {
+        if ((kk & 1) ? cs1 : cs0) cs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fx[0], cs, 0, 0, 0);
+      }
     }
   };
 
@@ -209,7 +229,17 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const int block_i
                acc[i][j][g * 4 + 3] * p.alpha};
     *reinterpret_cast<f32x4*>(cl + ml * BN + ((c ^ (ml & (CH - 1))) << 2)) = v;
   });
-  __syncthreads();
+  if constexpr (CS) {
+    // the waves' sums go behind the parked tile (TM = 2: csl[BM]; TM = 1: the two k halves csl[wn][BM]); one float atomic per column and
+    // block, BM consecutive columns
+    static_assert(BM * BN * 4 + 2 * BM * 4 <= 2 * STAGE, "column sums: room behind the parked tile");
+    float* const csl = reinterpret_cast<float*>(smem) + BM * BN;
+    if ((cs0 || cs1) && lane < 32) csl[TM == 2 ? wm * WM + wn * 32 + lane : wn * BM + wm * WM + lane] = cs[0];
+    __syncthreads();
+    if ((cs0 || cs1) && tid < BM && m0 + tid < p.M) atomicAdd(p.a_colsum + m0 + tid, TM == 2 ? csl[tid] : csl[tid] + csl[BM + tid]);
+  } else {
+    __syncthreads();
+  }
   PH_TL(5);
   // every read of the fused chain for ALL steps of this thread, requested before its first store (epilogue classes, gemm_common.h).  These
   // kernels run two blocks per CU on a 256-register budget: the reads are requested after the accumulators are parked (64 registers

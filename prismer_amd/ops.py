@@ -134,7 +134,9 @@ class WgradQueue:
     """Deferred weight gradients.  Nothing inside a step reads dW / db before the optimizer, so the wgrad GEMMs
     (dW += dY^T X: outputs of 18..144 tiles, alone they fill a fraction of the chip and need split-K + a reduce pass) and
     the bias column sums are queued and issued per reduction length K as ONE grouped launch each
-    (ph_gemm_grouped_bf16 / ph_colsum_grouped_bf16).  join_side() flushes, so every existing synchronisation point of the
+    (ph_gemm_grouped_bf16 / ph_colsum_grouped_bf16).  At flush() a queued column sum whose dy is the [K][M] operand of a queued GEMM rides
+    with that GEMM (ph_gemm_args.a_colsum: the sums are taken from the fragments the GEMM holds, dy is not read a second time); only the
+    entries without a partner go through ph_colsum_grouped_bf16.  join_side() flushes, so every existing synchronisation point of the
     programs still sees complete gradients.  Operand tensors stay referenced until their launch."""
 
     def __init__(self):
@@ -146,7 +148,7 @@ class WgradQueue:
         # > 0 (with eager_flush): mid-segment launches are BACKGROUND launches of at most this many blocks (each walks several
         # tiles), so the weight gradients trickle through the CUs the chain leaves idle; the flush at the segment end is uncapped
         self.bg_blocks = 0
-        self.gemms = {}          # K -> [(dy, x, gw, M, N, K)]
+        self.gemms = {}          # K -> [(dy, x, gw, M, N, K)] (flush() appends the paired bias gradient, or None, as a 7th element)
         self.cols = []           # [(dy, gb, M, N)]
         self.folds = []          # [(dshadow, dw, Cout, Cin, ks, Kp)]  conv weight gradients: shadow layout -> parameter layout
         self.lns = []            # [(partials, blocks, D, dgamma, dbeta)]  LayerNorm gamma / beta partial sums
@@ -234,16 +236,45 @@ class WgradQueue:
                 while i0 < len(allq) and len(q) < _lib.GEMM_GROUP_MAX and allq[i0][2].data_ptr() not in seen:
                     seen.add(allq[i0][2].data_ptr()); q.append(allq[i0]); i0 += 1
                 arr = (_lib.GemmArgs * len(q))()
-                for g, (dy, x, gw, M, N, Kk) in zip(arr, q):
+                ws = _workspace(q[0][0].device, 1)
+                for g, (dy, x, gw, M, N, Kk, *gb) in zip(arr, q):
                     g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), gw.data_ptr()
+                    g.a_colsum = ptr(gb[0]) if gb else None
+                    g.workspace, g.workspace_bytes = ws.data_ptr(), WS_BYTES
                     g.M, g.N, g.K = M, N, Kk
                     g.lda, g.ldb, g.ldc = dy.stride(0), x.stride(0), gw.stride(0)
                     # single-writer outputs of the native step are OVERWRITTEN (no read of the zeroed buffer, and AdamW does not
                     # have to zero it): self.exclusive is set by the Trainer for the duration of its own step only
                     acc = 0 if (excl is not None and gw.data_ptr() in excl) else 1
                     g.trans_a, g.trans_b, g.out_f32, g.accumulate, g.alpha = 1, 1, 1, acc, 1.0
+                # the workspace is for the persistent kernel's k-balanced plan only (partial tiles folded inside the launch); a group
+                # that plan leaves whole is issued without one, as before
+                units, split = C.c_int(0), C.c_int(0)
+                if max_blocks or lib.ph_gemm_grouped_plan(arr, len(q), C.byref(units), C.byref(split)) != 0 or split.value <= 1:
+                    for g in arr:
+                        g.workspace, g.workspace_bytes = None, 0
                 check(lib.ph_gemm_grouped_capped_bf16(arr, len(q), max_blocks, _stream()), 'ph_gemm_grouped_capped_bf16')
-        off_critical_path(work, *[t for e in allq for t in e[:3]])
+        off_critical_path(work, *[t for e in allq for t in e[:3]], *[e[6] for e in allq if len(e) > 6 and e[6] is not None])
+
+    def _pair_cols(self):
+        """column sums that can ride with a queued GEMM: same dy (address, row stride), rows = the GEMM's K, columns = its M.  Each cols entry
+        goes to ONE GEMM (the first free one that reads its dy), so a dy shared by two GEMMs is still summed once."""
+        if not self.cols or not self.gemms:
+            return
+        free = {}
+        for K, q in self.gemms.items():
+            for i, e in enumerate(q):
+                if len(e) == 6:
+                    free.setdefault((e[0].data_ptr(), e[0].stride(0), K, e[3]), []).append((K, i))
+        rest = []
+        for dy, gb, rows, N in self.cols:
+            slot = free.get((dy.data_ptr(), dy.stride(0), rows, N))
+            if slot and dy.dtype == BF16 and gb.dtype == F32 and gb.is_contiguous():
+                K, i = slot.pop(0)
+                self.gemms[K][i] = self.gemms[K][i] + (gb,)
+            else:
+                rest.append((dy, gb, rows, N))
+        self.cols = rest
 
     def _flush_cols(self):
         allq, self.cols = self.cols, []
@@ -260,6 +291,7 @@ class WgradQueue:
         off_critical_path(work, *[t for e in allq for t in e[:2]])
 
     def flush(self):
+        self._pair_cols()
         for K in list(self.gemms):
             self._flush_gemms(K)
         self._flush_cols()
