@@ -32,8 +32,8 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* ABI revision: bumped whenever an argument struct or a signature changes (101: ph_conv_gather window fields, ph_gemm_args row map +
  * defer_reduce; 102: round 4; 103: round 5 -- ph_ce_fwd takes a row_loss scratch, no memset nodes anywhere; 104: round 6 -- ph_dense_minmax_partial,
- * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
-#define PH_VERSION 105
+ * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; 106: ph_gemm_route replaces ph_gemm_grouped_plan; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
+#define PH_VERSION 106
 
 enum { PH_OK = 0, PH_ERR_BAD_ARG = -1, PH_ERR_UNSUPPORTED = -2, PH_ERR_LAUNCH = -3 };
 enum { PH_ACT_NONE = 0, PH_ACT_QUICKGELU = 1, PH_ACT_RELU2 = 2, PH_ACT_GELU = 3, PH_ACT_RELU = 4,
@@ -123,22 +123,44 @@ int ph_gemm_flush_deferred(hipStream_t stream);
  * block per CU.  With a `workspace` shared by all its problems and plain fp32 outputs, the tiles of a problem may also be cut over K so
  * that the units (problem, tile, k-range) of the whole group fill the 256 blocks evenly: every unit of a cut tile writes its fp32 tile
  * to the workspace, and the unit that finishes last sums them in split order and writes C (accumulate / alpha as usual) -- inside the
- * launch, no fold pass, bitwise reproducible.  Without a workspace, or one too small, the group runs whole.  ph_gemm_grouped_plan tells. */
+ * launch, no fold pass, bitwise reproducible.  Without a workspace, or one too small, the group runs whole.  ph_gemm_route tells. */
 int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream);
-/* tuning hook for benchmarks and tests: variant of the big-tile (256x128, LDS-DMA) kernel -- 0 = off, 1 = plain main loop, 5 / 6 = ping-pong
- * main loop with the LEAN tail (no surplus DMA, no drain; round 4), 7 = 6 with the LDS-DMA requests spread over the M phase (round 6, default) -- and the
- * tile count from which it is used (1 = every eligible launch, bypassing the dispatch cost model); a negative value leaves the setting unchanged.
- * The library reads no environment variable: the defaults (7, 128) are compiled in and this call is the only switch. */
+/* tuning hook for benchmarks and tests: main loop of the big-tile (256x128, LDS-DMA) kernels -- 0 = off, 1 = plain main loop (forward-shaped
+ * single launches; every other form runs it as lean), 2..6 = lean: ping-pong main loop, no surplus DMA, no drain, >= 7 = spread: lean with the
+ * LDS-DMA requests spread over the MFMA phase (default) -- and the tile count from which they are used (1 = every eligible launch, bypassing
+ * the dispatch cost model); a negative value leaves the setting unchanged.  The value is decoded once for the single, grouped and conv
+ * launches alike (the values 8..11 and >= 12, which nothing sets, ran lean on a single launch and spread on a grouped one before ABI 106:
+ * they are spread everywhere now).  The library reads no environment variable: the defaults (7, 128) are compiled in and this call is the
+ * only switch. */
 int ph_gemm_tuning(int big_mode, int big_min_tiles);
 /* same, as a BACKGROUND launch: at most `max_blocks` blocks (0 = one per tile), each walking several tiles.  Deferred weight
  * gradients issued beside the latency-bound backward chain of the decoder (roberta.py:212-231 in reverse) then fill the
  * idle CUs without taking every block slot from the chain's small kernels. */
 int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream);
-/* Host-only query: the plan ph_gemm_grouped_bf16 would use for this group on the persistent 256x128 weight-gradient kernel.  *units = work
- * units (problem, tile, k-range) of the launch, *max_split = the largest number of k-ranges any problem's tiles are cut into (1 = no
- * problem is split; partial sums of a split tile are folded inside the launch, in split order, by the unit that finishes last).
- * Both are 0 when the group does not take that kernel.  Launches nothing. */
-int ph_gemm_grouped_plan(const ph_gemm_args* args, int n, int* units, int* max_split);
+/* Host-only query: the route -- kernel, tile, splits, grid, fold pass -- the entry points above would take for these arguments under the
+ * current ph_gemm_tuning.  grouped == 0: ph_gemm_bf16 (n = 1); otherwise ph_gemm_grouped_capped_bf16 with `max_blocks` (0: ph_gemm_grouped_bf16).
+ * Needs no device and launches nothing: pointers are looked at for presence (and the workspaces of a group for being one buffer) only, and
+ * the device-resident zero page the LDS-DMA conv gather needs is taken to be there.  A ph_gemm_bf16 call that is cut in two by rows (tail
+ * split: the last partial row panels of a launch slightly above a whole number of block rounds go to a second, small call) answers
+ * parts = 2, rows [0, tail_m) and [tail_m, M), with the route of each. */
+/* kernel classes, in the order ph_gemm_dispatch_counts counts them */
+enum { PH_GEMM_CLS_128 = 0, PH_GEMM_CLS_64, PH_GEMM_CLS_KS2, PH_GEMM_CLS_BIG, PH_GEMM_CLS_BIG_GROUPED, PH_GEMM_CLS_GROUPED,
+       PH_GEMM_CLS_SPLITK_REDUCE, PH_GEMM_CLS_COUNT };
+/* how the partial sums of a k split are folded: not at all (no split, or fp32 atomics on C), by a pass right behind the launch, by a pass
+ * queued for ph_gemm_flush_deferred, or inside the launch by the unit of a tile that finishes last (persistent 256x128 kernel) */
+enum { PH_GEMM_FOLD_NONE = 0, PH_GEMM_FOLD_PASS, PH_GEMM_FOLD_DEFERRED, PH_GEMM_FOLD_IN_LAUNCH };
+typedef struct {
+  int cls;                        /* PH_GEMM_CLS_* of the GEMM launch */
+  int bm, bn;                     /* block tile */
+  int variant;                    /* 256x128 kernels: 1 plain, 2 lean, 3 spread main loop (see ph_gemm_tuning); 0 otherwise */
+  int units;                      /* blocks of the launch before any max_blocks cap; persistent 256x128 kernel: work units (problem, tile,
+                                     k-range) its 256 blocks walk */
+  int max_split;                  /* largest number of k-ranges any problem is cut into (1 = no problem is split) */
+  int fold, fold_lanes;           /* PH_GEMM_FOLD_*; threads per output vector of the fold pass (1 or 16), 0 without one */
+  int64_t ws_bytes;               /* bytes of `workspace` the route uses (arrival counters first, partial sums behind) */
+} ph_gemm_route_part;
+typedef struct { int parts, tail_m; ph_gemm_route_part part[2]; } ph_gemm_route_info;
+int ph_gemm_route(const ph_gemm_args* args, int n, int grouped, int max_blocks, ph_gemm_route_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (fp32 math, eps inside the sqrt).  Replaces model/modules/utils.py:14-19 (F.layer_norm in

@@ -60,6 +60,19 @@ class ColsumItem(C.Structure):
 
 
 GEMM_GROUP_MAX = 16      # PH_GEMM_GROUP_MAX
+GEMM_CLS = ('128x128', '64x64', 'ks2', 'big', 'big_grouped', 'grouped', 'splitk_reduce')     # PH_GEMM_CLS_*
+GEMM_CLS_BIG_GROUPED = GEMM_CLS.index('big_grouped')
+GEMM_FOLD_NONE, GEMM_FOLD_PASS, GEMM_FOLD_DEFERRED, GEMM_FOLD_IN_LAUNCH = 0, 1, 2, 3
+
+
+class GemmRoutePart(C.Structure):
+    _fields_ = [('cls', c_int), ('bm', c_int), ('bn', c_int), ('variant', c_int), ('units', c_int), ('max_split', c_int),
+                ('fold', c_int), ('fold_lanes', c_int), ('ws_bytes', c_i64)]
+
+
+class GemmRouteInfo(C.Structure):
+    _fields_ = [('parts', c_int), ('tail_m', c_int), ('part', GemmRoutePart * 2)]
+
 
 
 class ConvLayoutItem(C.Structure):
@@ -217,7 +230,7 @@ _SIGS = {
     'ph_conv_grad_from_shadow_grouped': (c_int, [c_void_p, c_int, c_void_p]),
     'ph_gemm_grouped_bf16': (c_int, [c_void_p, c_int, c_void_p]),
     'ph_gemm_grouped_capped_bf16': (c_int, [c_void_p, c_int, c_int, c_void_p]),
-    'ph_gemm_grouped_plan': (c_int, [c_void_p, c_int, C.POINTER(c_int), C.POINTER(c_int)]),
+    'ph_gemm_route': (c_int, [c_void_p, c_int, c_int, c_int, C.POINTER(GemmRouteInfo)]),
     'ph_gemm_tuning': (c_int, [c_int, c_int]),
     'ph_attention_tuning': (c_int, [c_int]),
     'ph_layernorm_tuning': (c_int, [c_int]),
@@ -263,7 +276,7 @@ def _load():
 
 lib, LIB_PATH = _load()
 GEMM_BIG_DEFAULT = (7, 128)    # ph_gemm_tuning(mode, min_tiles) values of the product dispatch (tests / probes restore them after an override)
-ABI_VERSION = 105          # PH_VERSION of include/prismer_hip.h these ctypes structures mirror
+ABI_VERSION = 106          # PH_VERSION of include/prismer_hip.h these ctypes structures mirror
 if lib.ph_version() != ABI_VERSION:
     raise ImportError(f'{LIB_PATH} reports ABI revision {lib.ph_version()}, this binding was written for {ABI_VERSION} '
                       '(stale build? run `python -m prismer_amd.build --force`)')

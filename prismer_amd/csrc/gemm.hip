@@ -81,17 +81,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(ReduceGroup 
 
 namespace phg { std::atomic<long long> g_gemm_counts[PH_GEMM_CLS_COUNT]; }
 // run-time tuning (ph_gemm_tuning); -1 = not set yet: the first reader takes the environment default
-static std::atomic<int> g_big_mode{-1}, g_big_min_tiles{-1};
-static int big_mode_now() {
-  int m = g_big_mode.load(std::memory_order_relaxed);
-  if (m < 0) m = 7;
-  return m;
-}
-static int big_min_tiles_now() {
-  int m = g_big_min_tiles.load(std::memory_order_relaxed);
-  if (m < 0) m = 128;
-  return m;
-}
+static std::atomic<int> g_big_mode{-1}, g_big_min_tiles{-1};      // (read by tuning_now below)
 
 // ---- deferred fold passes (ph_gemm_args.defer_reduce): one queue per process, see the header for the calling contract
 namespace {
@@ -225,29 +215,76 @@ static int fill_params(const ph_gemm_args* a, GemmParams& p) {
   return PH_OK;
 }
 
+// ================================================================================================================================
+// Dispatch: decide the route first, launch second.  route_single / route_grouped turn (arguments, tuning) into a Route -- kernel class, tile,
+// variant, per-problem k split, grid, fold pass, workspace layout -- with no HIP call, lock, counter or profiler (they run on a machine without
+// a device; ph_gemm_route hands the same value to the host); ph_gemm_bf16 / run_grouped execute a Route.  The rules in order: DESIGN.md section 3.
+
+// ---- fitted constants of the cost models (us; time of a launch = rounds x (fixed + k-tiles x per-k-tile)) -- every one named once.
+// The fixed parts of the single and of the grouped models DIFFER for what looks like the same quantity (12.0 / 14.0 for a 256x128 block, 12.0 /
+// 10.0 for a 128x128 round): each was fitted with its own dispatch rule and nobody has re-measured which is right, so both stay, under two names.
+namespace fit {
+// per-shape fit of DESIGN.md section 3 ("What the per-shape fit says about ALL these GEMMs"; profiles/r2_gemm_by_grid.txt)
+constexpr double BIG_KTILE = 0.67;            // a 256x128 LDS-DMA block alone on its CU
+constexpr double PAIR128_KTILE = 0.84;        // a pair of co-resident 128x128 blocks
+constexpr double LONE128_KTILE = 0.5;         // a lone 128x128 block (the last, half-empty round)
+constexpr double BIG_FIXED_SINGLE = 12.0, R128_FIXED_SINGLE = 12.0;          // ph_gemm_bf16: 256x128 against 128x128
+constexpr double NN_TIE = 1.02;               // ties go to the 256x128 kernel for [N,K] B (stem 25088x384x1728), against it for [K,N] B (LARGE dgrads)
+// the persistent weight-gradient plan (k-balanced plan): prologue + parking + write-out of a unit, slab write + read-back
+constexpr double BIG_FIXED_GROUPED = 14.0, BIG_SLAB = 6.0, R128_FIXED_GROUPED = 10.0;
+// register-staged tile / split-K model: slope probe 8320x768 NT, K 768 -> 3072 (profiles/r1_*): one wave of co-resident 128x128 blocks (2 per CU),
+// of 64x64 blocks (4 per CU), fixed part of a block wave; fold launch measured with rocprof + partial traffic in bytes per us
+constexpr double REG128_KTILE = 1.07, REG64_KTILE = 0.83, REG_WAVE_FIXED = 4.0, FOLD_LAUNCH = 8.0, FOLD_BYTES_PER_US = 3.0e6;
+}  // namespace fit
+// Floor of the persistent plan: a unit shorter than BIG_FIXED_GROUPED / BIG_KTILE = 21 k-tiles spends more time in the fixed part than in its k
+// loop, and every further cut ADDS more fixed time to the chip than it removes loop time from the longest block -- no k-range is shorter.
+constexpr int BIG_KT_FLOOR = 21, BIG_MAX_SPLIT = 32, BIG_MAX_UNITS = 8192;
+static_assert(BIG_KT_FLOOR * fit::BIG_KTILE >= fit::BIG_FIXED_GROUPED && (BIG_KT_FLOOR - 1) * fit::BIG_KTILE < fit::BIG_FIXED_GROUPED, "floor = fixed part / k-tile time");
+constexpr int SLOTS128 = 512, SLOTS64 = 1024;      // co-resident blocks of the chip: 2 x 128x128 or 4 x 64x64 per CU
+
+struct Tuning { int big_mode, big_min_tiles; bool zero_page; };      // zero_page: zero_bias_ptr() is there (the LDS-DMA conv gather reads it)
+static Tuning tuning_now(bool device) {
+  int m = g_big_mode.load(std::memory_order_relaxed), t = g_big_min_tiles.load(std::memory_order_relaxed);
+  return Tuning{m < 0 ? 7 : m, t < 0 ? 128 : t, !device || zero_bias_ptr() != nullptr};
+}
+
+constexpr int GMAX = PH_GEMM_GROUP_MAX;
+struct Route {
+  int cls = PH_GEMM_CLS_GROUPED, bm = 0, bn = 0;
+  BigVariant variant = BigVariant::off;            // 256x128 kernels only
+  int ta = 0, tb = 0, pf = 0, conv = 0;            // as the register-staged grouped launchers take them (pf: prefetch ring; conv: 1 gathered A, 2 gathered B)
+  int n = 1, max_blocks = 0;
+  int tiles_m[GMAX], tiles_n[GMAX], nsplit[GMAX], kt_per_split[GMAX];
+  int start[GMAX + 1];                                // first block (persistent kernel: unit) of problem i; start[n] = blocks / units of the launch
+  int max_split = 1;
+  int fold = PH_GEMM_FOLD_NONE, fold_lanes = 0;
+  size_t ws_bytes = 0, cnt_bytes = 0;              // workspace: arrival counters of all cut problems first (cnt_bytes), partial sums / slabs behind
+  size_t cnt_off[GMAX], ws_off[GMAX];
+  int tail_m = 0;                                  // ph_gemm_bf16: > 0 = the call is two calls, rows [0, tail_m) and [tail_m, M); nothing else is set
+  bool as_group = false;                           // ph_gemm_bf16: served as a group of one (conv NN, a_colsum)
+};
+
+static bool plain_f32(const ph_gemm_args& a) {     // the write-out a k split can fold: alpha x acc (+ C) in fp32
+  return a.out_f32 && !a.bias && a.act == PH_ACT_NONE && !a.pre_out && !a.act_in && !a.residual && !(a.drop_p > 0.f);
+}
+static int tiles_of(const ph_gemm_args& a, int bm, int bn) { return ceil_div(a.M, bm) * ceil_div(a.N, bn); }
+
 // ---- plan of a weight-gradient group on the persistent 256x128 kernel ---------------------------------------------------------
 // The kernel's 256 blocks walk the units of the group in order, block b takes units b, b + 256, ...; a unit is (problem, tile, k-range).
-// Cost of a unit from the per-shape fits: 0.67 us per k-tile + 14 us fixed (prologue, parking, write-out); a unit of a tile
-// that is cut over K also writes its fp32 tile as a slab and one unit per tile reads them all back: + BIG_SLAB_US.  The makespan is the
-// longest block.  Unsplit, a group of T tiles costs ceil(T / 256) rounds whatever T % 256 is; cutting every tile of problem i into ns_i
-// k-ranges lets the units of the whole group fill the rounds evenly.
-// Floor: a unit shorter than BIG_FIXED_US / BIG_KTILE_US = 21 k-tiles spends more time in the fixed part than in its k loop, and every
-// further cut ADDS more fixed time to the chip than it removes loop time from the longest block -- no k-range is shorter than that.
-constexpr double BIG_KTILE_US = 0.67, BIG_FIXED_US = 14.0, BIG_SLAB_US = 6.0;
-constexpr int BIG_KT_FLOOR = 21;      // ceil(BIG_FIXED_US / BIG_KTILE_US)
-constexpr int BIG_MAX_SPLIT = 32, BIG_MAX_UNITS = 8192;
-static_assert(BIG_KT_FLOOR * BIG_KTILE_US >= BIG_FIXED_US && (BIG_KT_FLOOR - 1) * BIG_KTILE_US < BIG_FIXED_US, "floor = fixed part / k-tile time");
-struct BigPlan { int ns[PH_GEMM_GROUP_MAX]; int units, max_split; double cost; size_t ws_bytes; };
+// Cost of a unit: BIG_KTILE per k-tile + BIG_FIXED_GROUPED; a unit of a tile that is cut over K also writes its fp32 tile as a slab and one
+// unit per tile reads them all back: + BIG_SLAB.  The makespan is the longest block.  Unsplit, a group of T tiles costs ceil(T / 256) rounds
+// whatever T % 256 is; cutting every tile of problem i into ns_i k-ranges lets the units of the whole group fill the rounds evenly.
+struct BigPlan { int ns[GMAX]; int units, max_split; double cost; size_t ws_bytes; };
 
 static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* units_out) {
   double load[256];
   for (int b = 0; b < 256; ++b) load[b] = 0.0;
   int u = 0;
   for (int i = 0; i < n; ++i) {
-    const int tiles = ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN), kt = args[i].K / BK;
+    const int tiles = tiles_of(args[i], big::BM, big::BN), kt = args[i].K / BK;
     for (int sp = 0; sp < ns[i]; ++sp) {
       const int len = kt / ns[i] + (sp < kt % ns[i] ? 1 : 0);
-      const double c = len * BIG_KTILE_US + BIG_FIXED_US + (ns[i] > 1 ? BIG_SLAB_US : 0.0);
+      const double c = len * fit::BIG_KTILE + fit::BIG_FIXED_GROUPED + (ns[i] > 1 ? fit::BIG_SLAB : 0.0);
       for (int t = 0; t < tiles; ++t, ++u) load[u & 255] += c;
     }
   }
@@ -256,45 +293,289 @@ static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* 
   *units_out = u;
   return worst;
 }
-// bytes of workspace a plan needs: per split problem one int counter per tile (256-B aligned block) + tiles x ns slabs of 256 x 128 fp32
-static size_t big_plan_ws(const ph_gemm_args* args, int n, const int* ns) {
-  size_t b = 0;
-  for (int i = 0; i < n; ++i) {
-    if (ns[i] <= 1) continue;
-    const size_t tiles = (size_t)ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
-    b += (tiles * 4 + 255) / 256 * 256 + tiles * ns[i] * (size_t)(big::BM * big::BN * 4);
-  }
-  return b;
-}
+// bytes of workspace per cut problem: one int counter per tile (256-B aligned block) + tiles x ns slabs of 256 x 128 fp32
+static size_t big_cnt_bytes(int tiles) { return ((size_t)tiles * 4 + 255) / 256 * 256; }
+static size_t big_slab_bytes(int tiles, int ns) { return (size_t)tiles * ns * (size_t)(big::BM * big::BN * 4); }
 static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split) {
   BigPlan best;
   int tiles_all = 0, kt_max = 0;
   for (int i = 0; i < n; ++i) {
     best.ns[i] = 1;
-    tiles_all += ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
+    tiles_all += tiles_of(args[i], big::BM, big::BN);
     kt_max = std::max(kt_max, args[i].K / BK);
   }
   best.max_split = 1; best.ws_bytes = 0;
   best.cost = big_makespan(args, n, best.ns, &best.units);
   // groups that fill whole rounds stay as they are
   if (!may_split || tiles_all % 256 == 0) return best;
-  const ph_gemm_args& a0 = args[0];
   // candidate c: k-ranges of about kt_max / c k-tiles for every problem of the group
   for (int c = 2; c <= BIG_MAX_SPLIT && kt_max / c >= BIG_KT_FLOOR; ++c) {
     BigPlan pl;
     const double L = (double)kt_max / c;
-    pl.max_split = 1;
+    pl.max_split = 1; pl.ws_bytes = 0;
     for (int i = 0; i < n; ++i) {
       const int kt = args[i].K / BK;
       pl.ns[i] = std::max(1, std::min({(int)lround(kt / L), kt / BIG_KT_FLOOR, BIG_MAX_SPLIT}));
       pl.max_split = std::max(pl.max_split, pl.ns[i]);
+      const int tiles = tiles_of(args[i], big::BM, big::BN);
+      if (pl.ns[i] > 1) pl.ws_bytes += big_cnt_bytes(tiles) + big_slab_bytes(tiles, pl.ns[i]);
     }
-    pl.ws_bytes = big_plan_ws(args, n, pl.ns);
-    if (pl.ws_bytes > (size_t)a0.workspace_bytes) continue;
+    if (pl.ws_bytes > (size_t)args[0].workspace_bytes) continue;
     pl.cost = big_makespan(args, n, pl.ns, &pl.units);
     if (pl.units <= BIG_MAX_UNITS && pl.cost < best.cost) best = pl;
   }
   return best;
+}
+
+// whole problems on bm x bn tiles, one block per tile: what every grouped route starts from
+static void whole_tiles(Route& r, const ph_gemm_args* args, int bm, int bn) {
+  r.bm = bm; r.bn = bn; r.max_split = 1;
+  int tot = 0;
+  for (int i = 0; i < r.n; ++i) {
+    r.tiles_m[i] = ceil_div(args[i].M, bm); r.tiles_n[i] = ceil_div(args[i].N, bn);
+    r.nsplit[i] = 1; r.kt_per_split[i] = ceil_div(args[i].K, BK);
+    r.start[i] = tot;
+    tot += r.tiles_m[i] * r.tiles_n[i];
+  }
+  r.start[r.n] = tot;
+}
+
+static Route route_grouped(const ph_gemm_args* args, int n, int max_blocks, const Tuning& t) {
+  Route r;
+  r.n = n; r.max_blocks = max_blocks; r.ta = args[0].trans_a; r.tb = args[0].trans_b;
+  const bool conv = args[0].conv != nullptr, tt = r.ta && r.tb;
+  const BigVariant big = big_variant(t.big_mode);
+  int kt_max = 0, t128 = 0;
+  bool kfull = true, thin = false;
+  // one workspace for the whole group and plain fp32 write-outs: what either k split needs
+  bool shared_ws = args[0].workspace && args[0].workspace_bytes > 0;
+  for (int i = 0; i < n; ++i) {
+    const ph_gemm_args& a = args[i];
+    kt_max = std::max(kt_max, ceil_div(a.K, BK));
+    t128 += tiles_of(a, 128, 128);
+    kfull = kfull && (a.K % BK) == 0;
+    thin = thin || a.M <= 64 || a.N <= 64;
+    shared_ws = shared_ws && a.workspace == args[0].workspace && plain_f32(a) && !a.col_stats && a.rowmap_wo == 0;
+  }
+  // 128x128 tiles (twice the arithmetic intensity per staged byte) unless the group is so small that they would leave most
+  // CUs idle; long reductions always take them (measured: 16 adaptor wgrads 768x384xK=8320 ran 440 us on 64x64 tiles)
+  const int bsel = (!thin && (t128 >= 192 || (kt_max >= 32 && t128 >= 64))) ? 128 : 64;
+  whole_tiles(r, args, bsel, bsel);
+  const int total = r.start[n];
+
+  // ---- weight-gradient groups with long reductions: the 256x128 ping-pong kernel, one persistent block per CU, units = (tile, k-range) ----
+  BigPlan plan;
+  bool use_big = false, big_first = false;
+  {
+    bool ok = big != BigVariant::off && !conv && max_blocks == 0 && tt;
+    bool roomy = true;            // every problem covers at least one whole 256x128 tile
+    int kt_min = 1 << 30;
+    for (int i = 0; i < n && ok; ++i) {
+      const ph_gemm_args& a = args[i];
+      ok = (a.K % BK) == 0 && (a.M % 8) == 0 && (a.N % 8) == 0 && a.M >= 8 && a.N >= 8 && !a.col_stats;
+      roomy = roomy && a.M >= big::BM && a.N >= big::BN;
+      kt_min = std::min(kt_min, a.K / BK);
+    }
+    if (ok && kt_min >= 32) {
+      // makespan of the persistent kernel under its best plan against rounds x (k loop + fixed part) of the 128x128 grouped kernel
+      plan = plan_big_wgrad(args, n, shared_ws);
+      const double cost_128 = bsel != 128 ? 1e30 : total <= 256 ? kt_max * fit::LONE128_KTILE + fit::R128_FIXED_GROUPED
+                                                                : ceil(total / (double)SLOTS128) * (kt_max * fit::PAIR128_KTILE + fit::R128_FIXED_GROUPED);
+      use_big = plan.cost < cost_128;
+      // a cut plan over whole tiles goes ahead of the register-staged split below (which is for outputs far smaller than a 256x128 tile:
+      // the stems' 96 x 32 weight gradients)
+      big_first = use_big && plan.max_split > 1 && roomy;
+    }
+  }
+  auto take_big = [&]() {
+    whole_tiles(r, args, big::BM, big::BN);
+    r.cls = PH_GEMM_CLS_BIG_GROUPED; r.variant = big == BigVariant::spread ? BigVariant::spread : BigVariant::lean;
+    r.max_split = plan.max_split; r.fold = plan.max_split > 1 ? PH_GEMM_FOLD_IN_LAUNCH : PH_GEMM_FOLD_NONE;
+    int tot = 0;
+    for (int i = 0; i < n; ++i) {
+      const int tiles = r.tiles_m[i] * r.tiles_n[i];
+      r.nsplit[i] = plan.ns[i]; r.kt_per_split[i] = ceil_div(args[i].K / BK, plan.ns[i]);
+      if (plan.ns[i] > 1) { r.cnt_off[i] = r.cnt_bytes; r.cnt_bytes += big_cnt_bytes(tiles); }
+      r.start[i] = tot;
+      tot += tiles * plan.ns[i];
+    }
+    r.start[n] = tot;
+    r.ws_bytes = r.cnt_bytes;
+    for (int i = 0; i < n; ++i) {
+      if (plan.ns[i] > 1) { r.ws_off[i] = r.ws_bytes; r.ws_bytes += big_slab_bytes(r.tiles_m[i] * r.tiles_n[i], plan.ns[i]); }
+    }
+    return r;
+  };
+  if (big_first) return take_big();
+  // ---- grouped AND split over K: weight-gradient groups with few output tiles and very long reductions -- the stems' conv weight
+  // gradients, 6 experts x (2..42 tiles over up to 6272 k-tiles).  Every problem is cut into pieces of ~W/slots k-tiles so that the whole
+  // group fills the chip once, partial sums go to the caller's workspace and ONE grouped pass folds them (plain fp32 epilogues only).
+  const int slots = bsel == 128 ? SLOTS128 : SLOTS64;
+  if (max_blocks == 0 && tt && shared_ws && total * 2 <= slots) {
+    double W = 0.0;
+    for (int i = 0; i < n; ++i) W += (double)r.tiles_m[i] * r.tiles_n[i] * ceil_div(args[i].K, BK);
+    const int L = std::max(8, (int)ceil(W / slots));            // k-tiles per block
+    int nsp[GMAX], max_split = 1;
+    size_t off = 0, offs[GMAX];
+    for (int i = 0; i < n; ++i) {
+      const int kti = ceil_div(args[i].K, BK);
+      const int ns = std::min(ceil_div(kti, L), std::max(1, kti / 4));
+      nsp[i] = ceil_div(kti, ceil_div(kti, std::max(1, ns)));
+      offs[i] = off;
+      if (nsp[i] > 1) off += ((size_t)nsp[i] * args[i].M * ((args[i].N + 3) / 4 * 4) * 4 + 255) / 256 * 256;
+      max_split = std::max(max_split, nsp[i]);
+    }
+    if (max_split > 1 && off <= (size_t)args[0].workspace_bytes) {
+      int tot = 0;
+      for (int i = 0; i < n; ++i) {
+        r.nsplit[i] = nsp[i]; r.kt_per_split[i] = ceil_div(ceil_div(args[i].K, BK), nsp[i]); r.ws_off[i] = offs[i];
+        r.start[i] = tot;
+        tot += r.tiles_m[i] * r.tiles_n[i] * nsp[i];
+      }
+      r.start[n] = tot;
+      r.pf = 0; r.conv = conv ? 2 : 0;
+      r.max_split = max_split; r.ws_bytes = off; r.fold = PH_GEMM_FOLD_PASS; r.fold_lanes = 1;
+      return r;
+    }
+  }
+  if (use_big) return take_big();
+  // ---- forward-shaped implicit convolutions with many rows and a long reduction (the stems' layers 2..4 and their data gradients): the
+  // 256x128 LDS-DMA kernel with the gather in the DMA source address (the register-staged gather kernel ran them at ~410 TFLOP/s)
+  if (conv && !r.ta && !r.tb && t.big_mode > 1 && max_blocks == 0) {
+    bool ok = t.zero_page;                                   // the gather's padding lanes read the zero page
+    for (int i = 0; i < n && ok; ++i) {
+      const ph_gemm_args& a = args[i];
+      ok = a.M >= big::BM && a.K >= 2 * BK && (a.N % 8) == 0 && a.N >= 8 && (a.ldb % 8) == 0 && a.split_k <= 1 &&
+           (int64_t)a.conv->B * a.conv->H * a.conv->W * a.conv->C < (1ll << 31);          // 32-bit element offsets in the gather
+    }
+    if (ok) {
+      whole_tiles(r, args, big::BM, big::BN);
+      r.cls = PH_GEMM_CLS_BIG_GROUPED; r.variant = big == BigVariant::spread ? BigVariant::spread : BigVariant::lean; r.conv = 1;
+      int blocks = 0;
+      for (int i = 0; i < n; ++i) {
+        r.start[i] = blocks;
+        blocks += big_xcd_grid(r.tiles_m[i], r.tiles_n[i]);          // (XCD shares, see big_tile: the blocks beyond a share exit)
+      }
+      r.start[n] = blocks;
+      return r;
+    }
+  }
+  // ---- register-staged grouped kernel, whole problems.  Gathered operand: forward (NN, A = im2col view, through the prefetch ring: the gather
+  // loads are unconditional, so the ring's straight-line bookkeeping holds for any K) or weight gradient (TT, B = im2col view, no ring); plain
+  // problems take the ring whenever every K is a multiple of BK
+  if (conv) { r.conv = r.ta ? 2 : 1; r.pf = r.ta ? 0 : 1; r.ta = r.tb = r.ta ? 1 : 0; }
+  else r.pf = kfull ? 1 : 0;
+  return r;
+}
+
+// ---- tail split: a launch whose tile count is a little above a whole number of block rounds pays a full extra round for a handful of tiles
+// (c_fc 8320 x 3072: 65 x 24 = 1560 tiles of 128x128 on 512 block slots = 3.05 rounds -> 4 tile times, ~95 us).  The rows that cause the
+// overshoot (the last, partial row panels) are cut off and computed by a second, small call: 8192 x 3072 = exactly 3 rounds (+ 128 x 3072 on
+// 64x64 tiles, ~10 us beside an otherwise idle chip).  Returns the first row of the second call, 0 = no split.
+static int tail_split_row(const ph_gemm_args& a) {
+  const int64_t tn128 = ceil_div(a.N, 128), tiles = (int64_t)ceil_div(a.M, 128) * tn128, slots = SLOTS128;
+  if (a.trans_a || a.conv || a.col_stats || a.drop_p > 0.0f || a.split_k > 0 || a.rowmap_wo != 0 || tiles <= slots || (a.K % BK) != 0) return 0;
+  const int64_t over = tiles % slots;
+  const int64_t m_main = (tiles / slots) * slots / tn128 * 128, m_rem = a.M - m_main;      // the row panels that fit the whole rounds
+  // worth it when the overshoot is small (<= 12 % of a round) and the cut-off part is itself a small problem
+  return (over > 0 && over * 100 <= slots * 12 && m_rem > 0 && m_rem <= 512 && (m_main % 256) == 0 && m_main >= 2048) ? (int)m_main : 0;
+}
+static void tail_split_args(const ph_gemm_args& a, int m_main, ph_gemm_args& b, ph_gemm_args& c) {
+  b = a; c = a;
+  b.M = m_main;
+  c.M = a.M - m_main;
+  c.A = (const char*)a.A + (size_t)m_main * a.lda * 2;
+  c.C = (char*)a.C + (size_t)m_main * a.ldc * (a.out_f32 ? 4 : 2);
+  if (a.pre_out) c.pre_out = (char*)a.pre_out + (size_t)m_main * a.ldc * 2;
+  if (a.act_in) c.act_in = (const char*)a.act_in + (size_t)m_main * a.ld_act * 2;
+  if (a.residual) c.residual = (const char*)a.residual + (size_t)m_main * a.ldr * (a.residual_f32 ? 4 : 2);
+}
+
+static Route route_single(const ph_gemm_args& a, const Tuning& t) {
+  Route r;
+  if ((r.tail_m = tail_split_row(a)) > 0) return r;
+  if ((a.conv && !a.trans_a && !a.trans_b) || a.a_colsum) {      // implicit-GEMM forward, fused column sums: the grouped kernels have them
+    r = route_grouped(&a, 1, 0, t);
+    r.as_group = true;
+    return r;
+  }
+  r.ta = a.trans_a; r.tb = a.trans_b; r.start[0] = 0; r.nsplit[0] = 1;
+  const BigVariant big = big_variant(t.big_mode);
+  const int kt = ceil_div(a.K, BK);
+  // ---- 256x128 LDS-DMA kernel: enough 256x128 tiles for the chip, and cheaper by block rounds than the 128x128 kernel (a tile count just
+  // above a multiple of 256 favours the latter: 41 x 8 tiles of 256x128 are two full rounds, 81 x 8 of 128x128 one pair round + one lone round)
+  const int64_t tbig = (int64_t)tiles_of(a, big::BM, big::BN);
+  bool big_cheaper = true;
+  if (t.big_min_tiles > 1) {
+    const double ktd = (double)(a.K / BK);
+    const int64_t t128b = (int64_t)tiles_of(a, 128, 128), rem = t128b % SLOTS128;
+    const double cost_big = (double)ceil_div64(tbig, 256) * (ktd * fit::BIG_KTILE + fit::BIG_FIXED_SINGLE);
+    const double cost_128 = (double)(t128b / SLOTS128) * (ktd * fit::PAIR128_KTILE + fit::R128_FIXED_SINGLE) +
+                            (rem > 256 ? ktd * fit::PAIR128_KTILE + fit::R128_FIXED_SINGLE : (rem > 0 ? ktd * fit::LONE128_KTILE + fit::R128_FIXED_SINGLE : 0.0));
+    big_cheaper = cost_big < cost_128 * (a.trans_b ? 1.0 : fit::NN_TIE);
+  }
+  const bool big_any = big != BigVariant::off && !a.conv && !a.col_stats && (a.K % BK) == 0 && a.split_k <= 0 && a.M >= big::BM && (a.N % 8) == 0 && a.N >= 8 && big_cheaper;
+  // forward-shaped (B = [N][K]) and dgrad-shaped (B = [K][N]) problems: only the launches with N <= 1024 or a long k loop keep their isolated
+  // gain inside the step (profiles/r2_ab_big_tile_gemm.txt, r2_gemm_by_grid.txt) -- the wide-N, K = 768 launches are write-out bound there
+  const bool big_fwd = big_any && !a.trans_a && a.K >= 2 * BK && tbig >= t.big_min_tiles && (tbig >= 192 || a.K >= 32 * BK || t.big_min_tiles <= 1);
+  // weight-gradient layout (A = [K][M], B = [K][N]) with a long reduction: same kernel, both operands through the transposing reads, ping-pong only
+  const bool big_wgrad = big_any && a.trans_a && a.trans_b && a.K >= 32 * BK && (a.M % 8) == 0 && tbig >= 64;
+  if (big_fwd || big_wgrad) {
+    r.cls = PH_GEMM_CLS_BIG; r.bm = big::BM; r.bn = big::BN;
+    r.variant = big_fwd ? big : (big == BigVariant::spread ? BigVariant::spread : BigVariant::lean);
+    r.tiles_m[0] = ceil_div(a.M, big::BM); r.tiles_n[0] = ceil_div(a.N, big::BN); r.kt_per_split[0] = a.K / BK;
+    r.start[1] = big_xcd_grid(r.tiles_m[0], r.tiles_n[0]);
+    return r;
+  }
+  // ---- register-staged kernels: 128x128 tiles when they fill the chip; otherwise split the K loop (partials -> workspace -> fold pass with the
+  // epilogue) so that >= ~2 blocks per CU are in flight; 64x64 tiles for genuinely small outputs.  (tile, split) by the fit::REG* model: waves of
+  // co-resident blocks x (k-tiles x slope + fixed), a split adds the fold launch plus splits*M*N*4 bytes of partial traffic
+  const int ldws = (a.N + 3) / 4 * 4;
+  const bool plain_acc = plain_f32(a) && a.accumulate;
+  auto ws_fits = [&](int sp) { return a.workspace && (int64_t)sp * a.M * ldws * 4 <= a.workspace_bytes; };
+  const int64_t t128 = tiles_of(a, 128, 128), t64 = tiles_of(a, 64, 64);
+  int BM = 128, splits = 1;
+  if (a.split_k > 0) {
+    splits = a.split_k;
+    if (a.M <= 64 || a.N <= 64 || t128 * splits < 128) BM = 64;
+  } else {
+    double best = 1e30;
+    const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256};   // (the stems' first-layer weight gradients:
+                                                                                       //  2 output tiles, 6272 k-tiles -- 48 splits left them at 94 us)
+    for (int bm = 64; bm <= 128; bm += 64) {
+      if (bm == 128 && (a.M <= 64 || a.N <= 64)) continue;
+      const double tiles = (double)(bm == 128 ? t128 : t64), cap = bm == 128 ? SLOTS128 : SLOTS64, t_iter = bm == 128 ? fit::REG128_KTILE : fit::REG64_KTILE;
+      for (int sp : cand) {
+        if (sp > 1 && (sp > kt / 2 || !(ws_fits(sp) || plain_acc))) continue;
+        double cost = ceil(tiles * sp / cap) * (ceil((double)kt / sp) * t_iter + fit::REG_WAVE_FIXED);
+        if (sp > 1) cost += fit::FOLD_LAUNCH + (double)sp * a.M * ldws * 4.0 / fit::FOLD_BYTES_PER_US;
+        if (cost < best) { best = cost; BM = bm; splits = sp; }
+      }
+    }
+  }
+  if (splits > kt) splits = kt;
+  // N = 64 mod 128 and narrow (the stems' N = 192 convs): 128x64 tiles cover N exactly instead of wasting half a column tile
+  // (100352x192x864: 71 -> 66 us); on every other shape the narrower wave tile (one B fragment per two MFMAs) loses
+  const int BN = (BM == 128 && splits == 1 && a.N % 128 == 64 && a.N <= 192) ? 64 : BM;
+  r.cls = BM == 64 ? PH_GEMM_CLS_64 : PH_GEMM_CLS_128; r.bm = BM; r.bn = BN;
+  r.tiles_m[0] = ceil_div(a.M, BM); r.tiles_n[0] = ceil_div(a.N, BN);
+  // 64x64-tile launches that leave CUs with a single block (the decoder's M = 960 rows): split the k loop inside the block instead
+  // of over gridDim.z + a fold launch.  also instead of a workspace split-K of a 64x64 launch
+  if (BM == 64 && BN == 64 && !a.conv && !a.col_stats && !a.trans_a && (a.K % BK) == 0 && kt >= 8 && a.split_k <= 0 && t64 <= 512) {
+    r.cls = PH_GEMM_CLS_KS2; r.kt_per_split[0] = kt;
+    r.start[1] = r.tiles_m[0] * r.tiles_n[0];
+    return r;
+  }
+  r.kt_per_split[0] = ceil_div(kt, splits);
+  r.nsplit[0] = r.max_split = splits = ceil_div(kt, r.kt_per_split[0]);
+  r.start[1] = r.tiles_m[0] * r.tiles_n[0] * splits;
+  if (splits > 1 && ws_fits(splits)) {          // (without a workspace: plain fp32 accumulation with atomics, no fold pass)
+    const bool wide = splits >= 32 && (int64_t)a.M * ((a.N + 3) / 4) <= 16384;       // many splits of a small output: 16 lanes per output vector
+    r.fold = a.defer_reduce ? PH_GEMM_FOLD_DEFERRED : PH_GEMM_FOLD_PASS; r.fold_lanes = wide ? 16 : 1;
+    r.ws_bytes = (size_t)splits * a.M * ldws * 4;
+    r.ws_off[0] = 0;                            // (a deferred call: behind the partial sums already queued, run_single knows where)
+  }
+  return r;
 }
 
 // the arrival counters of a cut plan are zeroed by this kernel ahead of EVERY launch, on the launch's stream (a kernel, not a memset node:
@@ -304,397 +585,143 @@ __global__ void zero_counters_kernel(int* cnt, int n) {
   if (i < n) cnt[i] = 0;
 }
 
-static int gemm_grouped_impl(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream, bool plan_only, int* plan_units, int* plan_split);
-
-extern "C" int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream) {
-  return gemm_grouped_impl(args, n, 0, stream, false, nullptr, nullptr);
-}
-extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream) {
-  return gemm_grouped_impl(args, n, max_blocks, stream, false, nullptr, nullptr);
-}
-extern "C" int ph_gemm_grouped_plan(const ph_gemm_args* args, int n, int* units, int* max_split) {
-  PH_CHECK_ARG(units && max_split, "ph_gemm_grouped_plan: null output");
-  *units = 0; *max_split = 0;
-  return gemm_grouped_impl(args, n, 0, nullptr, true, units, max_split);
-}
-
-static int gemm_grouped_impl(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream, bool plan_only, int* plan_units, int* plan_split) {
+static int run_grouped(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream) {
   PH_CHECK_ARG(args && n >= 1 && n <= PH_GEMM_GROUP_MAX, "ph_gemm_grouped_bf16: need 1..%d problems, got %d", PH_GEMM_GROUP_MAX, n);
   double flops = 0.0, bytes = 0.0;
-  double w128 = 0.0, w64 = 0.0, kt_max = 0.0;      // tile-iterations of work per tile shape
-  bool kfull = true, thin = false;
-  const bool conv = args[0].conv != nullptr;
   for (int i = 0; i < n; ++i) {
     PH_CHECK_ARG(args[i].trans_a == args[0].trans_a && args[i].trans_b == args[0].trans_b, "ph_gemm_grouped_bf16: mixed layouts in one group");
-    PH_CHECK_ARG((args[i].conv != nullptr) == conv, "ph_gemm_grouped_bf16: implicit-GEMM conv problems cannot share a group with plain ones");
+    PH_CHECK_ARG((args[i].conv != nullptr) == (args[0].conv != nullptr), "ph_gemm_grouped_bf16: implicit-GEMM conv problems cannot share a group with plain ones");
     flops += 2.0 * args[i].M * (double)args[i].N * args[i].K;
     bytes += 2.0 * ((double)args[i].M * args[i].K + (double)args[i].N * args[i].K + (double)args[i].M * args[i].N);
-    const double kt = ceil_div(args[i].K, BK);
-    w128 += (double)ceil_div(args[i].M, 128) * ceil_div(args[i].N, 128) * kt;
-    w64 += (double)ceil_div(args[i].M, 64) * ceil_div(args[i].N, 64) * kt;
-    kt_max = kt > kt_max ? kt : kt_max;
-    kfull = kfull && (args[i].K % BK) == 0;
-    thin = thin || args[i].M <= 64 || args[i].N <= 64;
   }
   char desc__[96];
-  if (g_ph_prof_enabled && !plan_only) snprintf(desc__, sizeof(desc__), "gemm grouped n=%d ta=%d tb=%d K0=%d", n, args[0].trans_a, args[0].trans_b, args[0].K);
-  ProfScope prof__(PH_FAM_GEMM, flops, bytes, stream, desc__, !plan_only);
-  // 128x128 tiles (twice the arithmetic intensity per staged byte) unless the group is so small that they would leave most
-  // CUs idle; long reductions always take them (measured: 16 adaptor wgrads 768x384xK=8320 ran 440 us on 64x64 tiles)
-  double t128 = 0.0;
-  for (int i = 0; i < n; ++i) t128 += (double)ceil_div(args[i].M, 128) * ceil_div(args[i].N, 128);
-  const int BMsel = (!thin && (t128 >= 192.0 || (kt_max >= 32.0 && t128 >= 64.0))) ? 128 : 64;
-  (void)w128; (void)w64;
+  if (g_ph_prof_enabled) snprintf(desc__, sizeof(desc__), "gemm grouped n=%d ta=%d tb=%d K0=%d", n, args[0].trans_a, args[0].trans_b, args[0].K);
+  ProfScope prof__(PH_FAM_GEMM, flops, bytes, stream, desc__);
   GroupParams g;                             // ~2.3 KB: copied into the kernel arguments by the launch
   g.n = n;
-  int total = 0;
   for (int i = 0; i < n; ++i) {
     int rc = fill_params(&args[i], g.p[i]);
     if (rc) return rc;
-    g.p[i].tiles_m = ceil_div(args[i].M, BMsel); g.p[i].tiles_n = ceil_div(args[i].N, BMsel);
-    g.p[i].k_tiles_per_split = ceil_div(args[i].K, BK);
-    g.tile_start[i] = total;
-    g.nsplit[i] = 1;
-    total += g.p[i].tiles_m * g.p[i].tiles_n;
   }
-  g.tile_start[n] = total;
-  // ---- weight-gradient groups with long reductions: the 256x128 ping-pong kernel, one persistent block per CU, units = (tile, k-range) ----
-  BigPlan plan;
-  bool use_big = false, big_first = false;
-  {
-    bool ok = big_mode_now() > 0 && !conv && max_blocks == 0 && args[0].trans_a && args[0].trans_b;
-    // the tiles may be cut over K when the caller hands every problem the same workspace and the write-out is the plain fp32 one
-    bool may_split = args[0].workspace && args[0].workspace_bytes > 0;
-    bool roomy = true;            // every problem covers at least one whole 256x128 tile
-    int kt_min = 1 << 30, kt_big = 0;
-    for (int i = 0; i < n && ok; ++i) {
-      const ph_gemm_args& a = args[i];
-      ok = (a.K % BK) == 0 && (a.M % 8) == 0 && (a.N % 8) == 0 && a.M >= 8 && a.N >= 8 && !a.col_stats;
-      may_split = may_split && a.workspace == args[0].workspace && a.out_f32 && !a.bias && a.act == PH_ACT_NONE && !a.pre_out && !a.act_in &&
-                  !a.residual && !(a.drop_p > 0.f) && a.rowmap_wo == 0;
-      roomy = roomy && a.M >= big::BM && a.N >= big::BN;
-      kt_min = min(kt_min, a.K / BK); kt_big = max(kt_big, a.K / BK);
-    }
-    if (ok && kt_min >= 32) {
-      // makespan of the persistent kernel under its best plan (plan_big_wgrad) against rounds x (k loop + fixed part) of the 128x128 grouped
-      // kernel: 0.84 us per k-tile and pair of co-resident 128x128 blocks (0.5 us for a lone one)
-      plan = plan_big_wgrad(args, n, may_split);
-      const int t128 = total;           // (tiles of the BMsel grid computed above; BMsel is 128 for these groups)
-      const double cost_128 = BMsel == 128 ? (t128 <= 256 ? kt_big * 0.5 + 10.0 : ceil(t128 / 512.0) * (kt_big * 0.84 + 10.0)) : 1e30;
-      use_big = plan.cost < cost_128;
-      // a cut plan over whole tiles goes ahead of the register-staged split below (which is for outputs far smaller than a 256x128 tile:
-      // the stems' 96 x 32 weight gradients)
-      big_first = use_big && plan.max_split > 1 && roomy;
-    }
+  const Route r = route_grouped(args, n, max_blocks, tuning_now(true));
+  const bool big = r.cls == PH_GEMM_CLS_BIG_GROUPED;
+  char* const ws = reinterpret_cast<char*>(args[0].workspace);
+  for (int i = 0; i < n; ++i) {
+    GemmParams& p = g.p[i];
+    p.tiles_m = r.tiles_m[i]; p.tiles_n = r.tiles_n[i]; p.k_tiles_per_split = r.kt_per_split[i];
+    g.nsplit[i] = r.nsplit[i]; g.tile_start[i] = r.start[i];
+    p.ws = r.nsplit[i] > 1 ? reinterpret_cast<float*>(ws + r.ws_off[i]) : nullptr;
+    p.tile_cnt = big && r.nsplit[i] > 1 ? reinterpret_cast<int*>(ws + r.cnt_off[i]) : nullptr;
+    if (big && r.conv) p.ldws = 0;
   }
-  auto launch_big = [&]() -> int {
-    if (plan_only) { *plan_units = plan.units; *plan_split = plan.max_split; return PH_OK; }
-    int tot = 0;
-    size_t off = 0;
-    char* const ws = reinterpret_cast<char*>(args[0].workspace);
-    for (int i = 0; i < n; ++i) {
-      const int tiles = ceil_div(args[i].M, big::BM) * ceil_div(args[i].N, big::BN);
-      g.p[i].tiles_m = ceil_div(args[i].M, big::BM); g.p[i].tiles_n = ceil_div(args[i].N, big::BN);
-      g.p[i].k_tiles_per_split = ceil_div(args[i].K / BK, plan.ns[i]);
-      g.p[i].ws = nullptr; g.p[i].tile_cnt = nullptr;
-      g.nsplit[i] = plan.ns[i];
-      if (plan.ns[i] > 1) {
-        // counters of all split problems first (zeroed by one small kernel), slabs behind them
-        g.p[i].tile_cnt = reinterpret_cast<int*>(ws + off);
-        off += ((size_t)tiles * 4 + 255) / 256 * 256;
-      }
-      g.tile_start[i] = tot;
-      tot += tiles * plan.ns[i];
-    }
-    g.tile_start[n] = tot;
-    if (off > 0) {
+  g.tile_start[n] = r.start[n];
+  if (big && r.conv) return big::launch_grouped_conv(g, r.start[n], r.variant, stream);
+  if (big) {
+    if (r.cnt_bytes > 0) {
       // zeroed on the stream ahead of EVERY launch (captured with the step): the counters of an earlier launch -- or of a launch that never
       // finished, or whatever the workspace held before -- are never trusted
-      const int words = (int)(off / 4);
+      const int words = (int)(r.cnt_bytes / 4);
       hipLaunchKernelGGL(zero_counters_kernel, dim3(ceil_div(words, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(ws), words);
       PH_LAUNCH_CHECK("zero_counters_kernel");
-      for (int i = 0; i < n; ++i) {
-        if (plan.ns[i] <= 1) continue;
-        const size_t tiles = (size_t)g.p[i].tiles_m * g.p[i].tiles_n;
-        g.p[i].ws = reinterpret_cast<float*>(ws + off);
-        off += tiles * plan.ns[i] * (size_t)(big::BM * big::BN * 4);
-      }
     }
-    return big::launch_grouped_wgrad(g, tot, big_mode_now() >= 7 ? 7 : 5, stream);
-  };
-  if (big_first) return launch_big();
-  // ---- grouped AND split over K (round 3): weight-gradient groups with few output tiles and very long reductions -- the stems' conv
-  // weight gradients, 6 experts x (2..42 tiles over up to 6272 k-tiles).  As single launches each of them split K on its own (28-92 us
-  // per launch at 5-60 % fill, 28 launches per step); here every problem is cut into pieces of ~W/slots k-tiles so that the whole
-  // group fills the chip once, partial sums go to the caller's workspace and ONE grouped pass folds them (plain fp32 epilogues only).
-  {
-    const ph_gemm_args& a0 = args[0];
-    bool ok = max_blocks == 0 && a0.trans_a && a0.trans_b && a0.workspace && a0.workspace_bytes > 0;
-    double W = 0.0;
-    for (int i = 0; i < n && ok; ++i) {
-      const ph_gemm_args& a = args[i];
-      ok = a.out_f32 && !a.bias && a.act == PH_ACT_NONE && !a.pre_out && !a.act_in && !a.residual && !(a.drop_p > 0.f) && !a.col_stats &&
-           a.rowmap_wo == 0 && a.workspace == a0.workspace;
-      W += (double)g.p[i].tiles_m * g.p[i].tiles_n * ceil_div(a.K, BK);
-    }
-    const double slots = BMsel == 128 ? 512.0 : 1024.0;
-    if (ok && total * 2 <= slots) {
-      const int L = std::max(8, (int)ceil(W / slots));            // k-tiles per block
-      int blocks = 0, nsp[PH_GEMM_GROUP_MAX];
-      size_t off = 0, offs[PH_GEMM_GROUP_MAX];
-      bool any = false;
-      for (int i = 0; i < n; ++i) {
-        const int kti = ceil_div(args[i].K, BK);
-        int ns = std::min(ceil_div(kti, L), std::max(1, kti / 4));
-        const int per = ceil_div(kti, std::max(1, ns));
-        ns = ceil_div(kti, per);
-        nsp[i] = ns; offs[i] = off;
-        if (ns > 1) { any = true; off += ((size_t)ns * args[i].M * ((args[i].N + 3) / 4 * 4) * 4 + 255) / 256 * 256; }
-        blocks += g.p[i].tiles_m * g.p[i].tiles_n * ns;
-      }
-      if (any && off <= (size_t)a0.workspace_bytes) {
-        if (plan_only) return PH_OK;
-        int tot = 0;
-        for (int i = 0; i < n; ++i) {
-          const int kti = ceil_div(args[i].K, BK);
-          g.nsplit[i] = nsp[i];
-          g.p[i].k_tiles_per_split = ceil_div(kti, nsp[i]);
-          g.p[i].ldws = (args[i].N + 3) / 4 * 4;
-          g.p[i].ws = nsp[i] > 1 ? reinterpret_cast<float*>(reinterpret_cast<char*>(a0.workspace) + offs[i]) : nullptr;
-          g.tile_start[i] = tot;
-          tot += g.p[i].tiles_m * g.p[i].tiles_n * nsp[i];
-        }
-        g.tile_start[n] = tot;
-        int rc;
-        rc = BMsel == 128 ? reg::launch_grouped_128(g, tot, 0, 1, 1, 0, conv ? 2 : 0, stream) : reg::launch_grouped_64(g, tot, 0, 1, 1, 0, conv ? 2 : 0, stream);
-        if (rc != PH_OK) return rc;
-        ReduceGroup r;
-        r.n = 0; r.blk_start[0] = 0;
-        for (int i = 0; i < n; ++i) {
-          if (nsp[i] <= 1) continue;
-          r.p[r.n] = g.p[i]; r.splits[r.n] = nsp[i];
-          r.blk_start[r.n + 1] = r.blk_start[r.n] + reduce_blocks(g.p[i], false);
-          ++r.n;
-        }
-        count_launch(PH_GEMM_CLS_SPLITK_REDUCE);
-        hipLaunchKernelGGL(splitk_reduce_grouped_kernel<1>, dim3(r.blk_start[r.n]), dim3(256), 0, stream, r);
-        PH_LAUNCH_CHECK("splitk_reduce_grouped_kernel");
-        return PH_OK;
-      }
-    }
+    return big::launch_grouped_wgrad(g, r.start[n], r.variant, stream);
   }
-  if (use_big) return launch_big();
-  if (plan_only) return PH_OK;
-  const int ta = args[0].trans_a, tb = args[0].trans_b;
-  // ---- forward-shaped implicit convolutions with many rows and a long reduction (the stems' layers 2..4 and their data gradients): the
-  // 256x128 LDS-DMA kernel with the gather in the DMA source address (round 4; the register-staged gather kernel ran them at ~410 TFLOP/s)
-  if (conv && !ta && !tb && big_mode_now() > 1 && max_blocks == 0) {
-    bool ok = zero_bias_ptr() != nullptr;                    // the gather's padding lanes read the zero page
-    for (int i = 0; i < n && ok; ++i) {
-      const ph_gemm_args& a = args[i];
-      ok = a.M >= big::BM && a.K >= 2 * BK && (a.N % 8) == 0 && a.N >= 8 && (a.ldb % 8) == 0 && a.split_k <= 1 &&
-           (int64_t)a.conv->B * a.conv->H * a.conv->W * a.conv->C < (1ll << 31);          // 32-bit element offsets in the gather
-    }
-    if (ok) {
-      int blocks = 0;
-      for (int i = 0; i < n; ++i) {
-        g.p[i].tiles_m = ceil_div(args[i].M, big::BM); g.p[i].tiles_n = ceil_div(args[i].N, big::BN);
-        g.p[i].k_tiles_per_split = ceil_div(args[i].K, BK);
-        g.p[i].ws = nullptr; g.p[i].ldws = 0;
-        g.tile_start[i] = blocks;
-        blocks += big_xcd_grid(g.p[i].tiles_m, g.p[i].tiles_n);          // (XCD shares, see big_tile: the blocks beyond a share exit)
-      }
-      g.tile_start[n] = blocks;
-      return big::launch_grouped_conv(g, blocks, big_mode_now() >= 7 ? 7 : 5, stream);
-    }
+  int rc = r.bm == 128 ? reg::launch_grouped_128(g, r.start[n], max_blocks, r.ta, r.tb, r.pf, r.conv, stream)
+                       : reg::launch_grouped_64(g, r.start[n], max_blocks, r.ta, r.tb, r.pf, r.conv, stream);
+  if (rc != PH_OK || r.fold == PH_GEMM_FOLD_NONE) return rc;
+  ReduceGroup red;                           // ONE grouped pass folds the partial sums of the problems that were cut
+  red.n = 0; red.blk_start[0] = 0;
+  for (int i = 0; i < n; ++i) {
+    if (r.nsplit[i] <= 1) continue;
+    red.p[red.n] = g.p[i]; red.splits[red.n] = r.nsplit[i];
+    red.blk_start[red.n + 1] = red.blk_start[red.n] + reduce_blocks(g.p[i], false);
+    ++red.n;
   }
-  if (conv) {               // gathered operand: forward (NN, A = im2col view) or weight gradient (TT, B = im2col view); no prefetch ring
-    PH_CHECK_ARG(ta == tb, "ph_gemm_grouped_bf16: conv gather needs the NN or the TT layout");
-    if (!ta) {
-      // gathered A operand through the register prefetch ring as well (round 3): the gather loads are unconditional (clamped address +
-      // select), so the ring's straight-line bookkeeping holds for any K
-      return BMsel == 128 ? reg::launch_grouped_128(g, total, max_blocks, 0, 0, 1, 1, stream)
-                          : reg::launch_grouped_64(g, total, max_blocks, 0, 0, 1, 1, stream);
-    }
-    return BMsel == 128 ? reg::launch_grouped_128(g, total, max_blocks, 1, 1, 0, 2, stream) : reg::launch_grouped_64(g, total, max_blocks, 1, 1, 0, 2, stream);
-  }
-  if (BMsel == 128) {
-    // prefetch ring for the [K,M] x [K,N] weight-gradient groups too (round 3: step -0.07 / -0.17 ms in two same-box pairs)
-    return reg::launch_grouped_128(g, total, max_blocks, ta, tb, kfull ? 1 : 0, 0, stream);
-  }
-  return reg::launch_grouped_64(g, total, max_blocks, ta, tb, kfull ? 1 : 0, 0, stream);
+  count_launch(PH_GEMM_CLS_SPLITK_REDUCE);
+  hipLaunchKernelGGL(splitk_reduce_grouped_kernel<1>, dim3(red.blk_start[red.n]), dim3(256), 0, stream, red);
+  PH_LAUNCH_CHECK("splitk_reduce_grouped_kernel");
+  return PH_OK;
+}
+
+extern "C" int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream) { return run_grouped(args, n, 0, stream); }
+extern "C" int ph_gemm_grouped_capped_bf16(const ph_gemm_args* args, int n, int max_blocks, hipStream_t stream) {
+  return run_grouped(args, n, max_blocks, stream);
 }
 
 extern "C" int ph_gemm_bf16(const ph_gemm_args* a, hipStream_t stream) {
   PH_CHECK_ARG(a && a->A && a->B && a->C, "ph_gemm_bf16: null pointer");
-  // ---- tail split (round 3): a launch whose tile count is a little above a whole number of block rounds pays a full extra round for
-  // a handful of tiles (c_fc 8320 x 3072: 65 x 24 = 1560 tiles of 128x128 on 512 block slots = 3.05 rounds -> 4 tile times, ~95 us).
-  // The rows that cause the overshoot (the last, partial row panels) are cut off and computed by a second, small launch:
-  // 8192 x 3072 = exactly 3 rounds (+ 128 x 3072 on 64x64 tiles, ~10 us beside an otherwise idle chip).
-  {   // (before the profiling scope of this call: the two halves are profiled as two launches)
-    const int64_t tn128 = ceil_div(a->N, 128), tm128 = ceil_div(a->M, 128);
-    const int64_t tiles = tm128 * tn128, slots = 512;
-    if (!a->trans_a && !a->conv && !a->col_stats && !(a->drop_p > 0.0f) && a->split_k <= 0 && a->rowmap_wo == 0 && tiles > slots && (a->K % BK) == 0) {
-      const int64_t over = tiles % slots;
-      const int64_t panels_main = (tiles / slots) * slots / tn128;              // row panels that fit the whole rounds
-      const int64_t m_main = panels_main * 128, m_rem = a->M - m_main;
-      // worth it when the overshoot is small (<= 12 % of a round) and the cut-off part is itself a small problem
-      if (over > 0 && over * 100 <= slots * 12 && m_rem > 0 && m_rem <= 512 && (m_main % 256) == 0 && m_main >= 2048) {
-        ph_gemm_args b = *a, c = *a;
-        b.M = (int)m_main;
-        c.M = (int)m_rem;
-        c.A = (const char*)a->A + (size_t)m_main * a->lda * 2;
-        c.C = (char*)a->C + (size_t)m_main * a->ldc * (a->out_f32 ? 4 : 2);
-        if (a->pre_out) c.pre_out = (char*)a->pre_out + (size_t)m_main * a->ldc * 2;
-        if (a->act_in) c.act_in = (const char*)a->act_in + (size_t)m_main * a->ld_act * 2;
-        if (a->residual) c.residual = (const char*)a->residual + (size_t)m_main * a->ldr * (a->residual_f32 ? 4 : 2);
-        int rc = ph_gemm_bf16(&b, stream);
-        if (rc != PH_OK) return rc;
-        return ph_gemm_bf16(&c, stream);
-      }
-    }
+  PH_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "ph_gemm_bf16: bad dims M=%d N=%d K=%d", a->M, a->N, a->K);      // (the route divides by them)
+  const Route r = route_single(*a, tuning_now(true));
+  if (r.tail_m > 0) {       // (before the profiling scope of this call: the two halves are profiled as two launches)
+    ph_gemm_args b, c;
+    tail_split_args(*a, r.tail_m, b, c);
+    int rc = ph_gemm_bf16(&b, stream);
+    return rc != PH_OK ? rc : ph_gemm_bf16(&c, stream);
   }
   char desc__[96];
   if (g_ph_prof_enabled) snprintf(desc__, sizeof(desc__), "gemm M=%d N=%d K=%d ta=%d tb=%d f32=%d acc=%d", a->M, a->N, a->K, a->trans_a, a->trans_b, a->out_f32, a->accumulate);
   ProfScope prof__(PH_FAM_GEMM, 2.0 * a->M * (double)a->N * a->K, 2.0 * ((double)a->M * a->K + (double)a->N * a->K + (double)a->M * a->N), stream, desc__);
-  if (a->conv && !a->trans_a && !a->trans_b) return ph_gemm_grouped_capped_bf16(a, 1, 0, stream);     // implicit-GEMM forward: grouped kernel
-  if (a->a_colsum) return ph_gemm_grouped_capped_bf16(a, 1, 0, stream);                               // fused column sums: grouped kernels
+  if (r.as_group) return run_grouped(a, 1, 0, stream);
   GemmParams p;
   {
     int rc = fill_params(a, p);
     if (rc) return rc;
   }
   PH_CHECK_ARG(!a->col_stats || a->split_k <= 1, "ph_gemm_bf16: col_stats cannot be combined with split-K");
-
-  // ---- big-tile LDS-DMA kernel: forward-shaped (both operands K-contiguous) GEMMs with enough 256x128 tiles for the chip ----
-  {
-    // g_big_mode (PH_GEMM_BIG / ph_gemm_tuning): 0 = off, 1 = plain main loop (round-2 first version), 5 = ping-pong main loop (the
-    // two waves of a SIMD alternate read and MFMA phases; retired in round 6, now = 6), 6 = ping-pong with the LEAN tail (no surplus DMA, no drain;
-    // round 4), 7 = 6 with the DMA requests spread over the M phase (default since round 6)
-    const int big_mode = big_mode_now(), big_min_tiles = big_min_tiles_now();
-    const int64_t tb = (int64_t)ceil_div(a->M, big::BM) * ceil_div(a->N, big::BN);
-    // block rounds of either kernel (constants from the per-shape fits, us): a 256x128 block alone on its CU, a pair of co-resident
-    // 128x128 blocks, a lone 128x128 block (what the last, half-empty round of that kernel is made of -- the reason a tile count just
-    // above a multiple of 256 favours it: 41 x 8 tiles of 256x128 are two full rounds, 81 x 8 of 128x128 one pair round + one lone round)
-    bool big_cheaper = true;
-    if (big_min_tiles > 1) {
-      const double ktd = (double)(a->K / BK);
-      const int64_t t128b = (int64_t)ceil_div(a->M, 128) * ceil_div(a->N, 128), rem = t128b % 512;
-      const double cost_big = (double)ceil_div64(tb, 256) * (ktd * 0.67 + 12.0);
-      const double cost_128 = (double)(t128b / 512) * (ktd * 0.84 + 12.0) + (rem > 256 ? ktd * 0.84 + 12.0 : (rem > 0 ? ktd * 0.5 + 12.0 : 0.0));
-      big_cheaper = cost_big < cost_128 * (a->trans_b ? 1.0 : 1.02);      // ties (two full rounds vs pair + lone round): measured in favour of
-                                                                           // the big kernel for [N,K] B (stem 25088x384x1728), against it for [K,N] B (LARGE dgrads)
-    }
-    if (big_mode > 0 && !a->conv && !a->col_stats && !a->trans_a && (a->K % BK) == 0 && a->K >= 2 * BK && a->split_k <= 0 && a->M >= big::BM &&
-        (a->N % 8) == 0 && a->N >= 8 && tb >= big_min_tiles && (tb >= 192 || a->K >= 32 * BK || big_min_tiles <= 1) && big_cheaper) {
-      // Forward-shaped (B = [N][K]) and dgrad-shaped (B = [K][N], trans_b) problems alike.  Isolated (tools/big_probe.py,
-      // profiles/r2_ab_big_tile_gemm.txt) the ping-pong kernel beats the 128x128 register-staged kernel on every shape of the
-      // step; inside the step (rocprofv3 per-grid durations, profiles/r2_gemm_by_grid.txt) only the launches with N <= 1024 or a
-      // long k loop keep the gain -- the wide-N, K = 768 launches are write-out bound there and the 2-blocks-per-CU kernel overlaps
-      // one tile's write-out with the other's main loop -- so those stay on the 128x128 kernel.
-      p.tiles_m = ceil_div(a->M, big::BM); p.tiles_n = ceil_div(a->N, big::BN);
-      p.k_tiles_per_split = a->K / BK;
-      p.ws = nullptr; p.ldws = 0;
-      return big::launch_single(p, big_mode == 1 ? 0 : (big_mode == 6 ? 5 : (big_mode >= 7 && big_mode <= 11 ? big_mode : 4)), false, a->trans_b != 0, stream);
-    }
-    // weight-gradient layout (A = [K][M], B = [K][N]) with a long reduction: same kernel, both operands through the transposing reads
-    if (big_mode > 0 && !a->conv && !a->col_stats && a->trans_a && a->trans_b && (a->K % BK) == 0 && a->K >= 32 * BK && a->split_k <= 0 &&
-        a->M >= big::BM && (a->M % 8) == 0 && (a->N % 8) == 0 && a->N >= 8 && tb >= 64 && big_cheaper) {
-      p.tiles_m = ceil_div(a->M, big::BM); p.tiles_n = ceil_div(a->N, big::BN);
-      p.k_tiles_per_split = a->K / BK;
-      p.ws = nullptr; p.ldws = 0;
-      return big::launch_single(p, big_mode >= 7 ? 7 : 5, true, true, stream);
-    }
+  const int splits = r.nsplit[0];
+  p.tiles_m = r.tiles_m[0]; p.tiles_n = r.tiles_n[0]; p.k_tiles_per_split = r.kt_per_split[0];
+  if (r.cls == PH_GEMM_CLS_BIG) {
+    p.ldws = 0;
+    return big::launch_single(p, r.variant, r.ta != 0, r.tb != 0, stream);
   }
-
-  // ---- tile shape and split-K selection -------------------------------------------------------------------------
-  // 128x128 tiles when they fill the chip; otherwise split the K loop (partials -> workspace -> reduce+epilogue) so
-  // that >= ~2 blocks per CU are in flight; 64x64 tiles for genuinely small outputs.
-  const int kt = ceil_div(a->K, BK);
-  const int ldws = (a->N + 3) / 4 * 4;
-  const bool plain_acc = !a->bias && !a->pre_out && !a->act_in && a->act == PH_ACT_NONE && !a->residual && !(a->drop_p > 0.0f) &&
-                         a->out_f32 && a->accumulate;
-  auto ws_fits = [&](int sp) { return a->workspace && (int64_t)sp * a->M * ldws * 4 <= a->workspace_bytes; };
-  const int64_t t128 = (int64_t)ceil_div(a->M, 128) * ceil_div(a->N, 128), t64 = (int64_t)ceil_div(a->M, 64) * ceil_div(a->N, 64);
-  // pick (tile, split) by a small cost model calibrated on the MI355X microbenchmarks (profiles/r1_*): a k-tile
-  // iteration costs ~1.5 us for co-resident 128x128 blocks (2 per CU) and ~0.5 us for 64x64 blocks (4 per CU);
-  // a split adds the reduce launch (~4 us) plus splits*M*N*4 bytes of partial traffic.
-  int BM = 128, BN = 0, splits = 1;      // BN = 0: square tile
-  if (a->split_k > 0) {
-    splits = a->split_k;
-    if (a->M <= 64 || a->N <= 64 || t128 * splits < 128) BM = 64;
-  } else {
-    double best = 1e30;
-    const int cand[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256};   // (the stems' first-layer weight gradients:
-                                                                                       //  2 output tiles, 6272 k-tiles -- 48 splits left them at 94 us)
-    for (int bm = 64; bm <= 128; bm += 64) {
-      if (bm == 128 && (a->M <= 64 || a->N <= 64)) continue;
-      // round-1 slope probe on MI355X: 8320x768 NT, K 768 -> 3072: 1.07 us per k-tile for one wave of co-resident
-      // 128x128 blocks (2 per CU), 0.83 us per k-tile and wave of 64x64 blocks (4 per CU); ~4 us fixed per block wave.
-      const double tiles = (double)(bm == 128 ? t128 : t64), cap = bm == 128 ? 512.0 : 1024.0, t_iter = bm == 128 ? 1.07 : 0.83;
-      for (int sp : cand) {
-        if (sp > 1 && (sp > kt / 2 || !(ws_fits(sp) || plain_acc))) continue;
-        double waves = ceil(tiles * sp / cap);
-        double cost = waves * (ceil((double)kt / sp) * t_iter + 4.0);
-        if (sp > 1) cost += 8.0 + (double)sp * a->M * ldws * 4.0 / 3.0e6;   // reduce launch: ~7 us measured (rocprof) + partial traffic
-        if (cost < best) { best = cost; BM = bm; splits = sp; }
+  if (r.cls == PH_GEMM_CLS_KS2) return reg::launch_ks2(p, r.tb, stream);
+  if (r.fold != PH_GEMM_FOLD_NONE) {
+    p.ws = (float*)a->workspace;
+    if (r.fold == PH_GEMM_FOLD_DEFERRED) {    // partial sums of consecutive deferred calls sit one after the other in the caller's workspace
+      std::lock_guard<std::mutex> lock(g_defer_mu);
+      const size_t need = (r.ws_bytes + 255) / 256 * 256;
+      if (g_defer.empty()) g_defer_cursor = 0;
+      if (!g_defer.empty() && (g_defer_ws != a->workspace || g_defer_cursor + need > (size_t)a->workspace_bytes)) {
+        int rcf = flush_deferred_locked(stream);
+        if (rcf != PH_OK) return rcf;
       }
+      p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + g_defer_cursor);
+      g_defer_cursor += need;
+      g_defer_ws = a->workspace;
     }
-  }
-  if (splits > kt) splits = kt;
-  // N = 64 mod 128 and narrow (the stems' N = 192 convs): 128x64 tiles cover N exactly instead of wasting half a column tile
-  // (100352x192x864: 71 -> 66 us); on every other shape the narrower wave tile (one B fragment per two MFMAs) loses
-  if (BN == 0 && BM == 128 && splits == 1 && a->N % 128 == 64 && a->N <= 192) BN = 64;
-  if (BN == 0) BN = BM;
-  p.tiles_m = ceil_div(a->M, BM); p.tiles_n = ceil_div(a->N, BN);
-  p.k_tiles_per_split = ceil_div(kt, splits);
-  splits = ceil_div(kt, p.k_tiles_per_split);
-  p.ws = nullptr; p.ldws = ldws;
-  bool deferred = false;
-  if (splits > 1) {
-    if (ws_fits(splits)) {
-      p.ws = (float*)a->workspace;
-      if (a->defer_reduce) {              // partial sums of consecutive deferred calls sit one after the other in the caller's workspace
-        std::lock_guard<std::mutex> lock(g_defer_mu);
-        const size_t need = ((size_t)splits * a->M * ldws * 4 + 255) / 256 * 256;
-        if (g_defer.empty()) g_defer_cursor = 0;
-        if (!g_defer.empty() && (g_defer_ws != a->workspace || g_defer_cursor + need > (size_t)a->workspace_bytes)) {
-          int rcf = flush_deferred_locked(stream);
-          if (rcf != PH_OK) return rcf;
-        }
-        p.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + g_defer_cursor);
-        g_defer_cursor += need;
-        g_defer_ws = a->workspace;
-        deferred = true;
-      }
-    } else PH_CHECK_ARG(plain_acc, "ph_gemm_bf16: split_k > 1 without workspace needs out_f32 + accumulate and no fused epilogue");
-  }
-  {
-    // 64x64-tile launches that leave CUs with a single block (the decoder's M = 960 rows): split the k loop inside the block instead
-    // of over gridDim.z + a reduce launch.  also instead of a workspace split-K of a 64x64 launch
-    const bool plain64 = BM == 64 && BN == 64 && !a->conv && !a->col_stats && !a->trans_a && (a->K % BK) == 0 && kt >= 8 && a->split_k <= 0;
-    if (plain64 && t64 <= 512) {
-      p.tiles_m = ceil_div(a->M, 64); p.tiles_n = ceil_div(a->N, 64);
-      p.k_tiles_per_split = kt; p.ws = nullptr;
-      return reg::launch_ks2(p, a->trans_b, stream);
-    }
-  }
-  int rc = BM == 64 ? reg::launch_single_64(p, a->trans_a, a->trans_b, splits, stream) : reg::launch_single_128(p, BN, a->trans_a, a->trans_b, splits, stream);
+  } else PH_CHECK_ARG(splits <= 1 || (plain_f32(*a) && a->accumulate), "ph_gemm_bf16: split_k > 1 without workspace needs out_f32 + accumulate and no fused epilogue");
+  int rc = r.bm == 64 ? reg::launch_single_64(p, r.ta, r.tb, splits, stream) : reg::launch_single_128(p, r.bn, r.ta, r.tb, splits, stream);
   if (rc != PH_OK || !p.ws) return rc;
-  const int64_t vecs = (int64_t)a->M * ((a->N + 3) / 4);
-  if (deferred) {                                         // the fold pass joins the queue (the partials stay where they are until the flush)
+  if (r.fold == PH_GEMM_FOLD_DEFERRED) {                  // the fold pass joins the queue (the partials stay where they are until the flush)
     std::lock_guard<std::mutex> lock(g_defer_mu);
-    g_defer.push_back(DeferredReduce{p, splits, splits >= 32 && vecs <= 16384});
+    g_defer.push_back(DeferredReduce{p, splits, r.fold_lanes == 16});
     return PH_OK;
   }
   count_launch(PH_GEMM_CLS_SPLITK_REDUCE);
-  if (splits >= 32 && vecs <= 16384) {                    // many splits of a small output: 16 lanes per output vector
-    int grid = (int)min((int64_t)2048, ceil_div64(vecs * 16, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel<16>, dim3(grid), dim3(256), 0, stream, p, splits);
-  } else {
-    int grid = (int)min((int64_t)2048, ceil_div64(vecs, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3(grid), dim3(256), 0, stream, p, splits);
-  }
+  if (r.fold_lanes == 16) hipLaunchKernelGGL(splitk_reduce_kernel<16>, dim3(reduce_blocks(p, true)), dim3(256), 0, stream, p, splits);
+  else hipLaunchKernelGGL(splitk_reduce_kernel<1>, dim3(reduce_blocks(p, false)), dim3(256), 0, stream, p, splits);
   PH_LAUNCH_CHECK("splitk_reduce_kernel");
+  return PH_OK;
+}
+
+extern "C" int ph_gemm_route(const ph_gemm_args* args, int n, int grouped, int max_blocks, ph_gemm_route_info* out) {
+  PH_CHECK_ARG(args && out && n >= 1 && n <= (grouped ? PH_GEMM_GROUP_MAX : 1), "ph_gemm_route: need 1..%d problems and an output", grouped ? PH_GEMM_GROUP_MAX : 1);
+  for (int i = 0; i < n; ++i) {
+    PH_CHECK_ARG(args[i].M > 0 && args[i].N > 0 && args[i].K > 0, "ph_gemm_route: bad dims M=%d N=%d K=%d", args[i].M, args[i].N, args[i].K);
+    PH_CHECK_ARG(args[i].trans_a == args[0].trans_a && args[i].trans_b == args[0].trans_b && (args[i].conv != nullptr) == (args[0].conv != nullptr) &&
+                 (!args[i].conv || args[i].trans_a == args[i].trans_b), "ph_gemm_route: mixed layouts in one group, or a conv gather on a layout that has none");
+  }
+  const Tuning t = tuning_now(false);
+  ph_gemm_args half[2];
+  Route r = grouped ? route_grouped(args, n, max_blocks, t) : route_single(args[0], t);
+  *out = ph_gemm_route_info{};
+  out->parts = r.tail_m > 0 ? 2 : 1; out->tail_m = r.tail_m;
+  if (r.tail_m > 0) tail_split_args(args[0], r.tail_m, half[0], half[1]);
+  for (int k = 0; k < out->parts; ++k) {
+    if (r.tail_m > 0 || k > 0) r = route_single(half[k], t);
+    ph_gemm_route_part& o = out->part[k];
+    o.cls = r.cls; o.bm = r.bm; o.bn = r.bn; o.variant = (int)r.variant; o.units = r.start[r.n]; o.max_split = r.max_split;
+    o.fold = r.fold; o.fold_lanes = r.fold_lanes; o.ws_bytes = (int64_t)r.ws_bytes;
+  }
   return PH_OK;
 }

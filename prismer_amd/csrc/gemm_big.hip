@@ -568,20 +568,21 @@ int launch_conv_t(const GroupParams& g, int blocks, hipStream_t s) {
   PH_LAUNCH_CHECK("gemm_big_conv_kernel");
   return PH_OK;
 }
-int launch_grouped_conv(const GroupParams& g, int blocks, int variant, hipStream_t s) {
-  return variant == 7 ? launch_conv_t<28>(g, blocks, s) : launch_conv_t<12>(g, blocks, s);
+int launch_grouped_conv(const GroupParams& g, int blocks, BigVariant v, hipStream_t s) {
+  return v == BigVariant::spread ? launch_conv_t<28>(g, blocks, s) : launch_conv_t<12>(g, blocks, s);
 }
 }  // namespace big
 
 namespace big {
-// variant: 0 = plain loop, 5 = ping-pong + LEAN tail (round 4), 7 = + SPREAD requests (round 6, default)
-int launch_single(const GemmParams& p, int variant, bool ta, bool tb, hipStream_t s) {
-  if (ta) return variant == 7 ? launch<28, true, true>(p, s) : launch<12, true, true>(p, s);      // weight-gradient layout: ping-pong only
-  if (tb) return variant == 0 ? launch<0, false, true>(p, s) : variant == 7 ? launch<28, false, true>(p, s) : launch<12, false, true>(p, s);
-  return variant == 0 ? launch<0, false, false>(p, s) : variant == 7 ? launch<28, false, false>(p, s) : launch<12, false, false>(p, s);
+// BigVariant (gemm_common.h) -> VARIANT: plain 0, lean 12, spread 28
+int launch_single(const GemmParams& p, BigVariant v, bool ta, bool tb, hipStream_t s) {
+  const bool plain = v == BigVariant::plain, spread = v == BigVariant::spread;
+  if (ta) return spread ? launch<28, true, true>(p, s) : launch<12, true, true>(p, s);      // weight-gradient layout: ping-pong only
+  if (tb) return plain ? launch<0, false, true>(p, s) : spread ? launch<28, false, true>(p, s) : launch<12, false, true>(p, s);
+  return plain ? launch<0, false, false>(p, s) : spread ? launch<28, false, false>(p, s) : launch<12, false, false>(p, s);
 }
-int launch_grouped_wgrad(const GroupParams& g, int total, int variant, hipStream_t s) {
-  return variant == 7 ? launch_grouped<28, true, true>(g, total, s) : launch_grouped<12, true, true>(g, total, s);
+int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, hipStream_t s) {
+  return v == BigVariant::spread ? launch_grouped<28, true, true>(g, total, s) : launch_grouped<12, true, true>(g, total, s);
 }
 }  // namespace big
 #ifdef PH_TIMELINE

@@ -702,9 +702,8 @@ struct GroupParams {
     static std::once_flag once__;                                                                                              \
     std::call_once(once__, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_expr), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes)); }); \
   } while (0)
-// launches per kernel class since the last reset (ph_gemm_dispatch_counts): lets a test assert WHICH kernels a program ran through
-enum { PH_GEMM_CLS_128 = 0, PH_GEMM_CLS_64, PH_GEMM_CLS_KS2, PH_GEMM_CLS_BIG, PH_GEMM_CLS_BIG_GROUPED, PH_GEMM_CLS_GROUPED,
-       PH_GEMM_CLS_SPLITK_REDUCE, PH_GEMM_CLS_COUNT };
+// launches per kernel class (PH_GEMM_CLS_*, prismer_hip.h) since the last reset (ph_gemm_dispatch_counts): lets a test assert WHICH kernels a
+// program ran through
 extern std::atomic<long long> g_gemm_counts[PH_GEMM_CLS_COUNT];
 inline void count_launch(int cls) { g_gemm_counts[cls].fetch_add(1, std::memory_order_relaxed); if (g_ph_prof_enabled) ::g_ph_prof_last_cls = cls; }
 
@@ -718,12 +717,19 @@ int launch_grouped_128(const GroupParams& g, int total, int max_blocks, int ta, 
 int launch_grouped_64(const GroupParams& g, int total, int max_blocks, int ta, int tb, int pf, int conv, hipStream_t s);
 }  // namespace reg
 
-// launchers of the 256x128 kernels (gemm_big.hip); variant: 0 plain main loop, 4 ping-pong, 5 ping-pong with the LEAN tail
+// main loop of the 256x128 kernels, decoded ONCE from the tuning value (ph_gemm_tuning big_mode) for the single, grouped and conv paths:
+// 0 off, 1 plain, 2..6 lean (ping-pong, no surplus DMA, no drain: VARIANT 12), >= 7 spread (lean + the DMA requests spread over the MFMA
+// phase: VARIANT 28, the default).  Only the forward-shaped single launch has the plain loop; everywhere else plain runs as lean.
+enum class BigVariant : int { off = 0, plain = 1, lean = 2, spread = 3 };
+inline BigVariant big_variant(int big_mode) {
+  return big_mode <= 0 ? BigVariant::off : big_mode == 1 ? BigVariant::plain : big_mode <= 6 ? BigVariant::lean : BigVariant::spread;
+}
+// launchers of the 256x128 kernels (gemm_big.hip)
 namespace big {
 constexpr int BM = 256, BN = 128;
-int launch_single(const GemmParams& p, int variant, bool ta, bool tb, hipStream_t s);
-int launch_grouped_wgrad(const GroupParams& g, int total, int variant, hipStream_t s);      // A = [K,M], B = [K,N], ping-pong, persistent grid
-int launch_grouped_conv(const GroupParams& g, int blocks, int variant, hipStream_t s);       // forward-shaped implicit-GEMM convolutions, one block per tile
+int launch_single(const GemmParams& p, BigVariant v, bool ta, bool tb, hipStream_t s);
+int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, hipStream_t s);      // A = [K,M], B = [K,N], ping-pong, persistent grid
+int launch_grouped_conv(const GroupParams& g, int blocks, BigVariant v, hipStream_t s);       // forward-shaped implicit-GEMM convolutions, one block per tile
 }  // namespace big
 
 }  // namespace phg

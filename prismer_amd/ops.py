@@ -249,8 +249,8 @@ class WgradQueue:
                     g.trans_a, g.trans_b, g.out_f32, g.accumulate, g.alpha = 1, 1, 1, acc, 1.0
                 # the workspace is for the persistent kernel's k-balanced plan only (partial tiles folded inside the launch); a group
                 # that plan leaves whole is issued without one, as before
-                units, split = C.c_int(0), C.c_int(0)
-                if max_blocks or lib.ph_gemm_grouped_plan(arr, len(q), C.byref(units), C.byref(split)) != 0 or split.value <= 1:
+                info = _lib.GemmRouteInfo()
+                if max_blocks or lib.ph_gemm_route(arr, len(q), 1, 0, C.byref(info)) != 0 or info.part[0].fold != _lib.GEMM_FOLD_IN_LAUNCH:
                     for g in arr:
                         g.workspace, g.workspace_bytes = None, 0
                 check(lib.ph_gemm_grouped_capped_bf16(arr, len(q), max_blocks, _stream()), 'ph_gemm_grouped_capped_bf16')

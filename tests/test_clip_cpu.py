@@ -18,7 +18,7 @@ def test_clip_symbols_resolve_and_ctl_layout_matches_header():
     from prismer_amd import _lib
     for name in ('ph_grad_sqnorm', 'ph_clip_finalize', 'ph_adamw_ctl'):
         assert name in _lib.EXPORTS and getattr(_lib.lib, name) is not None
-    assert _lib.lib.ph_version() == 105                                    # additions only: the revision does not move
+    assert _lib.lib.ph_version() == 106                                    # (these additions did not move the revision; 106 is ph_gemm_route)
     prog = r'''
 #include <stdio.h>
 #include <stddef.h>

@@ -129,4 +129,4 @@ def test_model_matches_the_sources():
     assert 'return tiles_m >= 8 && (share + 31) / 32 <= (big_xcd_even_share(tiles_m, tiles_n) + 31) / 32;' in common
     assert 'dim3(big_xcd_grid(p.tiles_m, p.tiles_n))' in big          # single launch: 8 x largest share
     assert 'big_tile<VARIANT, false, false, true, 1>(g.p[i], b - g.tile_start[i]);' in big    # grouped conv: per-problem numbering
-    assert 'blocks += big_xcd_grid(g.p[i].tiles_m, g.p[i].tiles_n);' in host
+    assert 'blocks += big_xcd_grid(r.tiles_m[i], r.tiles_n[i]);' in host

@@ -65,10 +65,12 @@ def group_args(probs, gws, gbs, ws, accumulate):
 
 
 def plan_of(arr):
+    """(units, max_split) of the group on the persistent 256x128 weight-gradient kernel, (0, 0) when it does not take that kernel"""
     from prismer_amd import _lib
-    units, split = C.c_int(-1), C.c_int(-1)
-    _lib.check(_lib.lib.ph_gemm_grouped_plan(arr, len(arr), C.byref(units), C.byref(split)), 'ph_gemm_grouped_plan')
-    return units.value, split.value
+    info = _lib.GemmRouteInfo()
+    _lib.check(_lib.lib.ph_gemm_route(arr, len(arr), 1, 0, C.byref(info)), 'ph_gemm_route')
+    part = info.part[0]
+    return (part.units, part.max_split) if part.cls == _lib.GEMM_CLS_BIG_GROUPED else (0, 0)
 
 
 def run(arr):
