@@ -123,7 +123,10 @@ int ph_gemm_flush_deferred(hipStream_t stream);
  * block per CU.  With a `workspace` shared by all its problems and plain fp32 outputs, the tiles of a problem may also be cut over K so
  * that the units (problem, tile, k-range) of the whole group fill the 256 blocks evenly: every unit of a cut tile writes its fp32 tile
  * to the workspace, and the unit that finishes last sums them in split order and writes C (accumulate / alpha as usual) -- inside the
- * launch, no fold pass, bitwise reproducible.  Without a workspace, or one too small, the group runs whole.  ph_gemm_route tells. */
+ * launch, no fold pass, bitwise reproducible.  Without a workspace, or one too small, the group runs whole.  ph_gemm_route tells.
+ * B may be the im2col view of an activation (`conv`, 3x3 or 1x1, C % 8 == 0, fewer than 2^31 elements: the stems' conv weight gradients, one
+ * group per layer): the gather is the source address of the kernel's LDS-DMA loads.  Such a group takes this kernel or the register-staged
+ * k split, whichever the cost model prices lower; a_colsum and dropout keep it off this kernel. */
 int ph_gemm_grouped_bf16(const ph_gemm_args* args, int n, hipStream_t stream);
 /* tuning hook for benchmarks and tests: main loop of the big-tile (256x128, LDS-DMA) kernels -- 0 = off, 1 = plain main loop (forward-shaped
  * single launches; every other form runs it as lean), 2..6 = lean: ping-pong main loop, no surplus DMA, no drain, >= 7 = spread: lean with the

@@ -226,6 +226,10 @@ static int fill_params(const ph_gemm_args* a, GemmParams& p) {
 namespace fit {
 // per-shape fit of DESIGN.md section 3 ("What the per-shape fit says about ALL these GEMMs"; profiles/r2_gemm_by_grid.txt)
 constexpr double BIG_KTILE = 0.67;            // a 256x128 LDS-DMA block alone on its CU
+// the same block with B gathered from an activation (CONV = 2).  Measured side by side on one uncut group (tools/stem_wgrad_probe.py,
+// profiles/stem_wgrad_ktile.txt): 0.881 us per k-tile gathered against 0.792 us plain, i.e. the gather costs the loop 11 %.  That probe's plain
+// figure is not the 0.67 of the per-shape fit every other constant here was fitted beside, so the SURCHARGE is what is used: 0.67 x 0.881 / 0.792
+constexpr double BIG_KTILE_GATHER = 0.745;
 constexpr double PAIR128_KTILE = 0.84;        // a pair of co-resident 128x128 blocks
 constexpr double LONE128_KTILE = 0.5;         // a lone 128x128 block (the last, half-empty round)
 constexpr double BIG_FIXED_SINGLE = 12.0, R128_FIXED_SINGLE = 12.0;          // ph_gemm_bf16: 256x128 against 128x128
@@ -276,7 +280,7 @@ static int tiles_of(const ph_gemm_args& a, int bm, int bn) { return ceil_div(a.M
 // whatever T % 256 is; cutting every tile of problem i into ns_i k-ranges lets the units of the whole group fill the rounds evenly.
 struct BigPlan { int ns[GMAX]; int units, max_split; double cost; size_t ws_bytes; };
 
-static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* units_out) {
+static double big_makespan(const ph_gemm_args* args, int n, const int* ns, double ktile, int* units_out) {
   double load[256];
   for (int b = 0; b < 256; ++b) load[b] = 0.0;
   int u = 0;
@@ -284,7 +288,7 @@ static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* 
     const int tiles = tiles_of(args[i], big::BM, big::BN), kt = args[i].K / BK;
     for (int sp = 0; sp < ns[i]; ++sp) {
       const int len = kt / ns[i] + (sp < kt % ns[i] ? 1 : 0);
-      const double c = len * fit::BIG_KTILE + fit::BIG_FIXED_GROUPED + (ns[i] > 1 ? fit::BIG_SLAB : 0.0);
+      const double c = len * ktile + fit::BIG_FIXED_GROUPED + (ns[i] > 1 ? fit::BIG_SLAB : 0.0);
       for (int t = 0; t < tiles; ++t, ++u) load[u & 255] += c;
     }
   }
@@ -296,7 +300,7 @@ static double big_makespan(const ph_gemm_args* args, int n, const int* ns, int* 
 // bytes of workspace per cut problem: one int counter per tile (256-B aligned block) + tiles x ns slabs of 256 x 128 fp32
 static size_t big_cnt_bytes(int tiles) { return ((size_t)tiles * 4 + 255) / 256 * 256; }
 static size_t big_slab_bytes(int tiles, int ns) { return (size_t)tiles * ns * (size_t)(big::BM * big::BN * 4); }
-static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split) {
+static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split, double ktile) {
   BigPlan best;
   int tiles_all = 0, kt_max = 0;
   for (int i = 0; i < n; ++i) {
@@ -305,7 +309,7 @@ static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split) {
     kt_max = std::max(kt_max, args[i].K / BK);
   }
   best.max_split = 1; best.ws_bytes = 0;
-  best.cost = big_makespan(args, n, best.ns, &best.units);
+  best.cost = big_makespan(args, n, best.ns, ktile, &best.units);
   // groups that fill whole rounds stay as they are
   if (!may_split || tiles_all % 256 == 0) return best;
   // candidate c: k-ranges of about kt_max / c k-tiles for every problem of the group
@@ -321,7 +325,7 @@ static BigPlan plan_big_wgrad(const ph_gemm_args* args, int n, bool may_split) {
       if (pl.ns[i] > 1) pl.ws_bytes += big_cnt_bytes(tiles) + big_slab_bytes(tiles, pl.ns[i]);
     }
     if (pl.ws_bytes > (size_t)args[0].workspace_bytes) continue;
-    pl.cost = big_makespan(args, n, pl.ns, &pl.units);
+    pl.cost = big_makespan(args, n, pl.ns, ktile, &pl.units);
     if (pl.units <= BIG_MAX_UNITS && pl.cost < best.cost) best = pl;
   }
   return best;
@@ -367,18 +371,25 @@ static Route route_grouped(const ph_gemm_args* args, int n, int max_blocks, cons
   BigPlan plan;
   bool use_big = false, big_first = false;
   {
-    bool ok = big != BigVariant::off && !conv && max_blocks == 0 && tt;
+    // a gathered B (the stems' 3x3 weight gradients: B = im2col view, k-row = output pixel) rides on the same units: the gather is the DMA
+    // source address, padding reads the zero page, element offsets are 32-bit
+    bool ok = big != BigVariant::off && (!conv || t.zero_page) && max_blocks == 0 && tt;
     bool roomy = true;            // every problem covers at least one whole 256x128 tile
     int kt_min = 1 << 30;
     for (int i = 0; i < n && ok; ++i) {
       const ph_gemm_args& a = args[i];
       ok = (a.K % BK) == 0 && (a.M % 8) == 0 && (a.N % 8) == 0 && a.M >= 8 && a.N >= 8 && !a.col_stats;
+      if (ok && conv) {
+        const ph_conv_gather& c = *a.conv;
+        ok = c.kh == 0 && (c.ks == 1 || c.ks == 3) && c.C > 0 && (c.C % 8) == 0 && !a.a_colsum && !(a.drop_p > 0.f) && c.H < (1 << 20) &&
+             (int64_t)c.B * c.H * c.W * c.C < (1ll << 31);
+      }
       roomy = roomy && a.M >= big::BM && a.N >= big::BN;
       kt_min = std::min(kt_min, a.K / BK);
     }
     if (ok && kt_min >= 32) {
       // makespan of the persistent kernel under its best plan against rounds x (k loop + fixed part) of the 128x128 grouped kernel
-      plan = plan_big_wgrad(args, n, shared_ws);
+      plan = plan_big_wgrad(args, n, shared_ws, conv ? fit::BIG_KTILE_GATHER : fit::BIG_KTILE);
       const double cost_128 = bsel != 128 ? 1e30 : total <= 256 ? kt_max * fit::LONE128_KTILE + fit::R128_FIXED_GROUPED
                                                                 : ceil(total / (double)SLOTS128) * (kt_max * fit::PAIR128_KTILE + fit::R128_FIXED_GROUPED);
       use_big = plan.cost < cost_128;
@@ -391,6 +402,7 @@ static Route route_grouped(const ph_gemm_args* args, int n, int max_blocks, cons
     whole_tiles(r, args, big::BM, big::BN);
     r.cls = PH_GEMM_CLS_BIG_GROUPED; r.variant = big == BigVariant::spread ? BigVariant::spread : BigVariant::lean;
     r.max_split = plan.max_split; r.fold = plan.max_split > 1 ? PH_GEMM_FOLD_IN_LAUNCH : PH_GEMM_FOLD_NONE;
+    r.conv = conv ? 2 : 0;
     int tot = 0;
     for (int i = 0; i < n; ++i) {
       const int tiles = r.tiles_m[i] * r.tiles_n[i];
@@ -426,6 +438,14 @@ static Route route_grouped(const ph_gemm_args* args, int n, int max_blocks, cons
       max_split = std::max(max_split, nsp[i]);
     }
     if (max_split > 1 && off <= (size_t)args[0].workspace_bytes) {
+      if (conv && use_big) {
+        // gathered groups choose between the two k splits by modelled cost, not by rule order (layer 2 of the stems, M = 192, is not "roomy" and
+        // still far cheaper on the persistent units): one wave of co-resident register-staged blocks of L k-tiles + the fold pass and its traffic
+        double part_bytes = 0.0;
+        for (int i = 0; i < n; ++i) part_bytes += nsp[i] > 1 ? (double)nsp[i] * args[i].M * ((args[i].N + 3) / 4 * 4) * 4.0 : 0.0;
+        const double cost_split = L * (bsel == 128 ? fit::REG128_KTILE : fit::REG64_KTILE) + fit::REG_WAVE_FIXED + fit::FOLD_LAUNCH + part_bytes / fit::FOLD_BYTES_PER_US;
+        if (plan.cost < cost_split) return take_big();
+      }
       int tot = 0;
       for (int i = 0; i < n; ++i) {
         r.nsplit[i] = nsp[i]; r.kt_per_split[i] = ceil_div(ceil_div(args[i].K, BK), nsp[i]); r.ws_off[i] = offs[i];
@@ -612,10 +632,10 @@ static int run_grouped(const ph_gemm_args* args, int n, int max_blocks, hipStrea
     g.nsplit[i] = r.nsplit[i]; g.tile_start[i] = r.start[i];
     p.ws = r.nsplit[i] > 1 ? reinterpret_cast<float*>(ws + r.ws_off[i]) : nullptr;
     p.tile_cnt = big && r.nsplit[i] > 1 ? reinterpret_cast<int*>(ws + r.cnt_off[i]) : nullptr;
-    if (big && r.conv) p.ldws = 0;
+    if (big && r.conv == 1) p.ldws = 0;
   }
   g.tile_start[n] = r.start[n];
-  if (big && r.conv) return big::launch_grouped_conv(g, r.start[n], r.variant, stream);
+  if (big && r.conv == 1) return big::launch_grouped_conv(g, r.start[n], r.variant, stream);
   if (big) {
     if (r.cnt_bytes > 0) {
       // zeroed on the stream ahead of EVERY launch (captured with the step): the counters of an earlier launch -- or of a launch that never
@@ -624,7 +644,7 @@ static int run_grouped(const ph_gemm_args* args, int n, int max_blocks, hipStrea
       hipLaunchKernelGGL(zero_counters_kernel, dim3(ceil_div(words, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(ws), words);
       PH_LAUNCH_CHECK("zero_counters_kernel");
     }
-    return big::launch_grouped_wgrad(g, r.start[n], r.variant, stream);
+    return big::launch_grouped_wgrad(g, r.start[n], r.variant, r.conv == 2, stream);
   }
   int rc = r.bm == 128 ? reg::launch_grouped_128(g, r.start[n], max_blocks, r.ta, r.tb, r.pf, r.conv, stream)
                        : reg::launch_grouped_64(g, r.start[n], max_blocks, r.ta, r.tb, r.pf, r.conv, stream);

@@ -37,8 +37,9 @@ typedef __attribute__((address_space(3))) void lptr_t;
 template <int VARIANT, bool TA, bool TB, bool XCD_REMAP, int CONV = 0, bool WG = false>
 __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id, const int kt0 = 0, const int nk_unit = 0, const int split = 0,
                                          const int nsplit = 1) {
-  static_assert(CONV == 0 || (CONV == 1 && !TA && !TB && (VARIANT & 4)), "conv gather: A of a forward-shaped problem, ping-pong loop");
-  static_assert(!WG || (TA && TB && CONV == 0 && !XCD_REMAP && (VARIANT & 12) == 12), "k-range units: weight-gradient layout, ping-pong loop, LEAN tail");
+  static_assert(CONV == 0 || (CONV == 1 && !TA && !TB && (VARIANT & 4)) || (CONV == 2 && TA && TB && WG),
+                "conv gather: A of a forward-shaped problem (ping-pong loop), or B of a weight-gradient unit");
+  static_assert(!WG || (TA && TB && CONV != 1 && !XCD_REMAP && (VARIANT & 12) == 12), "k-range units: weight-gradient layout, ping-pong loop, LEAN tail");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // tile mapping.  Hardware places block b on XCD b % 8, each XCD with its own 4-MB L2.  One-tile-per-block launches (XCD_REMAP) give every
   // XCD WHOLE row panels: XCD x owns tiles_m / 8 (+1) consecutive 256-row panels with ALL their column tiles, so an A panel is fetched
@@ -90,7 +91,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   const bf16* a_src[A_INSTR];
   const bf16* b_src[B_INSTR];
   // CONV: per row of the lane (loop invariant) the element offset of tap (0,0) and a 9-bit mask of the taps that fall inside the image
-  int row_off[CONV ? A_INSTR : 1], tap_ok[CONV ? A_INSTR : 1];
+  int row_off[CONV == 1 ? A_INSTR : 1], tap_ok[CONV == 1 ? A_INSTR : 1];
   // the lane's k chunk inside a k-tile is the same for all of its instructions: ((i*8 + wave)*8 + (lane>>3)) >> 1 & 7 does not depend on i
   const int conv_k = (((lane & 7) ^ ((wave * 4 + (lane >> 4)) & 7))) * 8;
   if constexpr (CONV == 1) {
@@ -119,9 +120,30 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
       a_src[i] = p.A + (size_t)min(m0 + r, p.M - 1) * p.lda + c * 8;
     }
   }
+  // CONV == 2 (the stems' 3x3 weight gradients on the k-range units): B is the im2col view with the OUTPUT PIXEL as k-row and (tap, channel) as
+  // column.  In the [K][N] image below a lane's column chunk c does not depend on the instruction (kr & 3 == (lane >> 4) & 3 for both) and its
+  // two k-rows lie 32 apart, so the (tap, channel) of the chunk is a loop invariant (ColTap's job in the register-staged kernels) and only the
+  // two pixels change per k-tile.  g_coff: element offset of the chunk from the pixel's (oy * stride, ox * stride); g_tap: the tap's input
+  // offset (pad included), x in the low byte and y above it (one register: the kernel has none to spare).  A chunk outside 9 C or N gets a y
+  // offset no image reaches (G_NOTAP; the host keeps H below it) and so reads the zero page like a tap outside the image.
+  constexpr int G_NOTAP = 1 << 20;
+  int g_coff = 0, g_tap = 0;
+  if constexpr (CONV == 2) {
+    const int pos = lane & 15, c = (((pos >> 2) ^ ((lane >> 4) & 3)) << 2) | (pos & 3);
+    const int col = n0 + c * 8;
+    const bool cin = col < p.cv.Kreal && col < p.N;
+    const int cc = cin ? col : 0;
+    const int tap = fdiv(cc, p.cv.C, p.cv.inv_c);
+    const int ky = p.cv.ks == 3 ? (tap >= 6 ? 2 : (tap >= 3 ? 1 : 0)) : 0, kx = tap - ky * p.cv.ks;
+    const int ty = ky + p.cv.offy, tx = kx + p.cv.offx;
+    g_coff = (ty * p.cv.W + tx) * p.cv.C + (cc - tap * p.cv.C);
+    g_tap = (cin ? ty : G_NOTAP) * 256 + (tx & 0xff);
+  }
 #pragma unroll
   for (int i = 0; i < B_INSTR; ++i) {
-    if constexpr (TB) {   // B = [K][N]: one instruction = 4 k-rows x 256 B; lane -> k-row (lane >> 4), LDS slot lane & 15 holds chunk c
+    if constexpr (CONV == 2) {
+      b_src[i] = nullptr;
+    } else if constexpr (TB) {   // B = [K][N]: one instruction = 4 k-rows x 256 B; lane -> k-row (lane >> 4), LDS slot lane & 15 holds chunk c
       const int kr = (i * 8 + wave) * 4 + (lane >> 4), pos = lane & 15;
       const int c = (((pos >> 2) ^ (kr & 3)) << 2) | (pos & 3);
       b_src[i] = p.B + (size_t)(kr + (WG ? kt0 * BK : 0)) * p.ldb + min(n0 + c * 8, p.N - 8);
@@ -134,15 +156,22 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   // CONV: the gathered source addresses of k-tile kt.  ~60 VALU instructions per wave: inside the ping-pong loop they run in the R phase
   // (beside the fragment reads), NOT in front of the MFMAs of the M phase -- the phases are barrier-locked, so VALU work at the head of
   // an M phase idles the matrix pipe of the SIMD for its whole length (first build: 440 instead of 660 TFLOP/s on the 384->768 layer).
-  const bf16* a_nxt[CONV ? A_INSTR : 1];
+  const bf16* a_nxt[CONV == 1 ? A_INSTR : 1];
   const bf16* b_nxt[CONV ? B_INSTR : 1];
   // every scalar the per-tile address work needs is pinned in SGPRs up front: left to itself the compiler re-reads them from the kernel
   // arguments inside the loop (s_load + s_waitcnt lgkmcnt(0) in the middle of the fragment reads) and turns the selects into branches
   int cvW = p.cv.W, cvC = p.cv.C, cvKreal = p.cv.Kreal, cvkw = p.cv.kw, Kfull = p.K;
   float cv_inv_c = p.cv.inv_c;
-  const bf16* conv_x = p.A;
+  const bf16* conv_x = CONV == 2 ? p.B : p.A;
   const bf16* zero_pg = p.zero16 + lane * 8;          // (a wave's padding lanes read 64 different 16-B pieces of the zero page, not one address)
   if constexpr (CONV == 1) asm volatile("" : "+s"(cvW), "+s"(cvC), "+s"(cvKreal), "+s"(cvkw), "+s"(Kfull), "+s"(cv_inv_c), "+s"(conv_x));
+  // CONV == 2: the pixel decomposition of the lane's two k-rows per k-tile needs these
+  int cvH = p.cv.H, cvHoWo = p.cv.Ho * p.cv.Wo, cvWo = p.cv.Wo, cvStride = p.cv.stride, m_first = kt0 * BK;
+  float cv_inv_howo = p.cv.inv_howo, cv_inv_wo = p.cv.inv_wo;
+  const bf16* zero16_base = p.zero16;
+  if constexpr (CONV == 2)
+    asm volatile("" : "+s"(cvW), "+s"(cvC), "+s"(cvH), "+s"(cvHoWo), "+s"(cvWo), "+s"(cvStride), "+s"(m_first), "+s"(cv_inv_howo), "+s"(cv_inv_wo), "+s"(conv_x),
+                 "+s"(zero16_base));
   // conv_prep(kt) is called for kt = 0, 1, 2, ... in order (every wave requests its tiles in order; at the tail the clamped index
   // repeats, see below).  C % 64 == 0 (192, 384, 768: every stem layer but the 96-channel one): a k-tile lies inside ONE tap, so the
   // (tap, channel) bookkeeping is wave-uniform and kept incrementally on the SALU -- no per-lane division; a state that has run past the
@@ -150,6 +179,28 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   const bool conv_c64 = CONV == 1 && (cvC & 63) == 0 && (cvKreal & 63) == 0;
   int s_ky = 0, s_kx = 0, s_c0 = 0, s_tap = 0;
   auto conv_prep = [&](int kt) {
+    if constexpr (CONV == 2) {
+      // k-row -> output pixel (b, oy, ox) -> element offset of the lane's chunk, or the zero page.  K % 64 == 0 (host): every k-row is a pixel.
+      const int mb = m_first + kt * BK + wave * 4 + (lane >> 4);
+      const int ty = g_tap >> 8, tx = (int)(signed char)(g_tap & 0xff);
+      // (the zero-page address is rebuilt per k-tile -- two VALU instructions -- instead of living in a register pair across the whole unit,
+      //  write-out included: with it the kernel spilled)
+      int zoff = lane * 8;
+      asm volatile("" : "+v"(zoff));
+      const bf16* const zpg = zero16_base + zoff;
+#pragma unroll
+      for (int i = 0; i < B_INSTR; ++i) {
+        const int m = mb + i * 32;
+        const int b = fdiv(m, cvHoWo, cv_inv_howo), rem = m - b * cvHoWo;
+        const int oy = fdiv(rem, cvWo, cv_inv_wo), ox = rem - oy * cvWo;
+        const int y0 = oy * cvStride, x0 = ox * cvStride;
+        const bool ok = (unsigned)(y0 + ty) < (unsigned)cvH && (unsigned)(x0 + tx) < (unsigned)cvW;
+        const bf16* src = conv_x + (((b * cvH + y0) * cvW + x0) * cvC + g_coff);      // (32-bit element offsets: the host keeps the tensor below 2^31)
+        b_nxt[i] = ok ? src : zpg;
+      }
+#pragma unroll
+      for (int i = 0; i < B_INSTR; ++i) asm volatile("" : "+v"(b_nxt[i]));
+    }
     if constexpr (CONV == 1) {
       const int koff = kt * BK;
       const int k = koff + conv_k;
@@ -185,19 +236,17 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
     char* sa = smem + stage * STAGE;
     char* sb = sa + A_BYTES;
     const int koff = kt * BK;
-    if constexpr (CONV == 1) {          // sources prepared by conv_prep(kt) (ping-pong loop: in the R phase, see there)
+    // CONV: sources prepared by conv_prep(kt) (ping-pong loop: in the R phase, see there) -- both operands for CONV == 1, B alone for CONV == 2
 #pragma unroll
-      for (int i = 0; i < A_INSTR; ++i) __builtin_amdgcn_global_load_lds((gptr_t*)a_nxt[i], (lptr_t*)(sa + (i * 8 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-      for (int i = 0; i < B_INSTR; ++i) __builtin_amdgcn_global_load_lds((gptr_t*)b_nxt[i], (lptr_t*)(sb + (i * 8 + wave) * 1024), 16, 0, 0);
-      return;
+    for (int i = 0; i < A_INSTR; ++i) {
+      if constexpr (CONV == 1) __builtin_amdgcn_global_load_lds((gptr_t*)a_nxt[i], (lptr_t*)(sa + (i * 8 + wave) * 1024), 16, 0, 0);
+      else __builtin_amdgcn_global_load_lds((gptr_t*)(a_src[i] + (TA ? (size_t)koff * p.lda : (size_t)koff)), (lptr_t*)(sa + (i * 8 + wave) * 1024), 16, 0, 0);
     }
 #pragma unroll
-    for (int i = 0; i < A_INSTR; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t*)(a_src[i] + (TA ? (size_t)koff * p.lda : (size_t)koff)), (lptr_t*)(sa + (i * 8 + wave) * 1024), 16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < B_INSTR; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t*)(b_src[i] + (TB ? (size_t)koff * p.ldb : (size_t)koff)), (lptr_t*)(sb + (i * 8 + wave) * 1024), 16, 0, 0);
+    for (int i = 0; i < B_INSTR; ++i) {
+      if constexpr (CONV != 0) __builtin_amdgcn_global_load_lds((gptr_t*)b_nxt[i], (lptr_t*)(sb + (i * 8 + wave) * 1024), 16, 0, 0);
+      else __builtin_amdgcn_global_load_lds((gptr_t*)(b_src[i] + (TB ? (size_t)koff * p.ldb : (size_t)koff)), (lptr_t*)(sb + (i * 8 + wave) * 1024), 16, 0, 0);
+    }
   };
 
   // one DMA instruction of a tile (round 6, VARIANT & 16: the six requests of a k-tile are spread over the M phase, one behind every
@@ -208,10 +257,11 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
     char* sa = smem + stage * STAGE;
     char* sb = sa + A_BYTES;
     const int koff = kt * BK;
-    if constexpr (CONV == 1) {          // sources prepared by conv_prep(kt) in the R phase
-      if constexpr (idx < A_INSTR) __builtin_amdgcn_global_load_lds((gptr_t*)a_nxt[idx], (lptr_t*)(sa + (idx * 8 + wave) * 1024), 16, 0, 0);
-      else __builtin_amdgcn_global_load_lds((gptr_t*)b_nxt[idx - A_INSTR], (lptr_t*)(sb + ((idx - A_INSTR) * 8 + wave) * 1024), 16, 0, 0);
-    } else if constexpr (idx < A_INSTR)
+    if constexpr (CONV == 1 && idx < A_INSTR)          // (CONV: sources prepared by conv_prep(kt) in the R phase)
+      __builtin_amdgcn_global_load_lds((gptr_t*)a_nxt[idx], (lptr_t*)(sa + (idx * 8 + wave) * 1024), 16, 0, 0);
+    else if constexpr (CONV != 0 && idx >= A_INSTR)
+      __builtin_amdgcn_global_load_lds((gptr_t*)b_nxt[idx - A_INSTR], (lptr_t*)(sb + ((idx - A_INSTR) * 8 + wave) * 1024), 16, 0, 0);
+    else if constexpr (idx < A_INSTR)
       __builtin_amdgcn_global_load_lds((gptr_t*)(a_src[idx] + (TA ? (size_t)koff * p.lda : (size_t)koff)), (lptr_t*)(sa + (idx * 8 + wave) * 1024), 16, 0, 0);
     else
       __builtin_amdgcn_global_load_lds((gptr_t*)(b_src[idx - A_INSTR] + (TB ? (size_t)koff * p.ldb : (size_t)koff)), (lptr_t*)(sb + ((idx - A_INSTR) * 8 + wave) * 1024), 16, 0, 0);
@@ -228,7 +278,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   // hold the same two A fragments and share the duty: wave wn takes fragment wn (one accumulator, 16 registers).  The MFMAs go into the M phase, whose
   // length is set by the partner wave's fragment reads (the loop is LDS bound), not into the R phase, where VALU conversions and adds would
   // lengthen the bound itself; nothing is added at the head of the phase.
-  const bool do_cs = WG && p.a_colsum != nullptr && tn == 0;
+  const bool do_cs = WG && CONV == 0 && p.a_colsum != nullptr && tn == 0;          // (the host rejects a_colsum together with a gather)
   const bf16x8 ones = __builtin_bit_cast(bf16x8, u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u});
   f32x16 cs = f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool cs0 = do_cs && wn == 0, cs1 = do_cs && wn == 1;
@@ -328,7 +378,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
 #pragma unroll
         for (int j = 0; j < 2; ++j) fw[kk][j] = TB ? frag_ks_dma<256>(lb, wn * 64 + j * 32, kk, lane) : frag_kc(lb, wn * 64 + j * 32, kk, lane);
       }
-      if constexpr (CONV == 1 && ISS0) {
+      if constexpr (CONV != 0 && ISS0) {
         // the sources of the tile this wave requests in M(t), worked out while the fragments arrive, behind ALL 16 fragment reads (interleaved,
         // the VALU work delays their issue).  Measured on the 384->768 layer, one problem (tools/conv_probe.py; the materialised im2col
         // matrix through the plain kernel: 44 us): in front of the MFMAs of the M phase 64 us (VALU at the head of a barrier-locked phase
@@ -421,7 +471,7 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
   const bool slab = WG && nsplit > 1;
   if (!slab) wo_prefetch<BM, BN, NTHR>(epi, p, m0, n0, PH_WO_ARGS);
   DropCtx dc;
-  const bool drop = p.drop_p > 0.0f;
+  const bool drop = CONV != 2 && p.drop_p > 0.0f;          // (the host keeps dropout off the gathered units: its Philox state is registers they do not have)
   if (drop) dc = make_drop(p.drop_seed, p.drop_stream, p.drop_p);
   constexpr int CH = BN / 4;
   float* cl = reinterpret_cast<float*>(smem);
@@ -478,20 +528,25 @@ __device__ __forceinline__ void big_tile(const GemmParams& p, const int block_id
       f32x4 sum[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) sum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // (CONV == 2 reads a slab in two halves: 32 registers fewer at the kernel's register peak, which the gather's loop invariants pushed over)
+      constexpr int FV = CONV == 2 ? VEC / 2 : VEC;
       for (int sp = 0; sp < nsplit; ++sp) {
         const float* src = tile_ws + (size_t)sp * TILE;
-        f32x4 v[VEC];
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) v[i] = *reinterpret_cast<const f32x4*>(src + (i * NTHR + (int)threadIdx.x) * 4);
+        for (int h = 0; h < VEC; h += FV) {
+          f32x4 v[FV];
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) sum[i] += v[i];
+          for (int i = 0; i < FV; ++i) v[i] = *reinterpret_cast<const f32x4*>(src + ((h + i) * NTHR + (int)threadIdx.x) * 4);
+#pragma unroll
+          for (int i = 0; i < FV; ++i) sum[h + i] += v[i];
+        }
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) *reinterpret_cast<f32x4*>(cl + (i * NTHR + (int)threadIdx.x) * 4) = sum[i];
       __syncthreads();
     }
   }
-  tile_writeout<BM, BN, NTHR>(PH_TL_ARG epi, p, cl, m0, n0, false, drop, dc, PH_WO_ARGS);
+  tile_writeout<BM, BN, NTHR, 1, CONV == 2 ? 2 : 4>(PH_TL_ARG epi, p, cl, m0, n0, false, drop, dc, PH_WO_ARGS);
   if constexpr (CONV == 1) {
     if (p.col_stats) tile_colstats<BM, BN, NTHR>(p, cl, m0, n0);       // train-mode BatchNorm sums from the parked tile
   }
@@ -523,7 +578,7 @@ int launch(const GemmParams& p, hipStream_t s) {
 // walks the tiles round by round; within a round the XCD-contiguous numbering of gemm_tile is kept (tiles that share an operand
 // panel run on one XCD at the same time).
 namespace big {
-template <int VARIANT, bool TA, bool TB>
+template <int VARIANT, bool TA, bool TB, int CONV>
 __global__ __launch_bounds__(NTHR) void gemm_big_grouped_kernel(GroupParams g) {
   const int total = g.tile_start[g.n], grid = gridDim.x;
   int i = 0;
@@ -537,15 +592,15 @@ __global__ __launch_bounds__(NTHR) void gemm_big_grouped_kernel(GroupParams g) {
     // into nsplit ranges that differ by at most one k-tile
     const int local = t - g.tile_start[i], ns = g.nsplit[i], ntile = g.p[i].tiles_m * g.p[i].tiles_n;
     const int sp = local / ntile, kt = g.p[i].K / BK, kq = kt / ns, kr = kt - kq * ns;
-    big_tile<VARIANT, TA, TB, false, 0, true>(g.p[i], local - sp * ntile, sp * kq + min(sp, kr), kq + (sp < kr ? 1 : 0), sp, ns);
+    big_tile<VARIANT, TA, TB, false, CONV, true>(g.p[i], local - sp * ntile, sp * kq + min(sp, kr), kq + (sp < kr ? 1 : 0), sp, ns);
     __syncthreads();                     // the write-out's LDS staging area is the next tile's DMA ring
   }
 }
-template <int VARIANT, bool TA, bool TB>
+template <int VARIANT, bool TA, bool TB, int CONV>
 int launch_grouped(const GroupParams& g, int total, hipStream_t s) {
-  PH_SET_SMEM_ONCE((&gemm_big_grouped_kernel<VARIANT, TA, TB>), SMEM);
+  PH_SET_SMEM_ONCE((&gemm_big_grouped_kernel<VARIANT, TA, TB, CONV>), SMEM);
   count_launch(PH_GEMM_CLS_BIG_GROUPED);
-  hipLaunchKernelGGL((gemm_big_grouped_kernel<VARIANT, TA, TB>), dim3(total < 256 ? total : 256), dim3(NTHR), SMEM, s, g);
+  hipLaunchKernelGGL((gemm_big_grouped_kernel<VARIANT, TA, TB, CONV>), dim3(total < 256 ? total : 256), dim3(NTHR), SMEM, s, g);
   PH_LAUNCH_CHECK("gemm_big_grouped_kernel");
   return PH_OK;
 }
@@ -581,8 +636,9 @@ int launch_single(const GemmParams& p, BigVariant v, bool ta, bool tb, hipStream
   if (tb) return plain ? launch<0, false, true>(p, s) : spread ? launch<28, false, true>(p, s) : launch<12, false, true>(p, s);
   return plain ? launch<0, false, false>(p, s) : spread ? launch<28, false, false>(p, s) : launch<12, false, false>(p, s);
 }
-int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, hipStream_t s) {
-  return v == BigVariant::spread ? launch_grouped<28, true, true>(g, total, s) : launch_grouped<12, true, true>(g, total, s);
+int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, bool gathered_b, hipStream_t s) {
+  if (gathered_b) return v == BigVariant::spread ? launch_grouped<28, true, true, 2>(g, total, s) : launch_grouped<12, true, true, 2>(g, total, s);
+  return v == BigVariant::spread ? launch_grouped<28, true, true, 0>(g, total, s) : launch_grouped<12, true, true, 0>(g, total, s);
 }
 }  // namespace big
 #ifdef PH_TIMELINE

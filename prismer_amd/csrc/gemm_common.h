@@ -728,7 +728,7 @@ inline BigVariant big_variant(int big_mode) {
 namespace big {
 constexpr int BM = 256, BN = 128;
 int launch_single(const GemmParams& p, BigVariant v, bool ta, bool tb, hipStream_t s);
-int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, hipStream_t s);      // A = [K,M], B = [K,N], ping-pong, persistent grid
+int launch_grouped_wgrad(const GroupParams& g, int total, BigVariant v, bool gathered_b, hipStream_t s);      // A = [K,M], B = [K,N] (or its im2col view), ping-pong, persistent grid
 int launch_grouped_conv(const GroupParams& g, int blocks, BigVariant v, hipStream_t s);       // forward-shaped implicit-GEMM convolutions, one block per tile
 }  // namespace big
 

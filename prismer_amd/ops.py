@@ -40,7 +40,8 @@ WS_BYTES = 256 << 20
 def _workspace(device, which=0):
     """per-(device, stream) fp32 scratch for split-K partial tiles / LayerNorm partials: kernels on one stream are
     serialised, so one buffer per stream is race-free (allocated once, reused by every launch on that stream).
-    which = 1: the separate buffer that holds the partial sums of DEFERRED fold passes until gemm_flush_deferred()"""
+    which = 1: the separate buffer that holds the partial sums of DEFERRED fold passes until gemm_flush_deferred()
+    which = 2: counters and slabs of the stems' grouped conv weight gradients (conv_wgrad_persistent)"""
     key = (device, _raw_stream(device.index if device.index is not None else _cur_device()), which)
     ws = _WS.get(key)
     if ws is None:
@@ -570,23 +571,53 @@ def wgrad_split_grouped(items):
         idx = [i for i, it in enumerate(items) if (it[5] is not None) == want_conv]
         for i0 in range(0, len(idx), _lib.GEMM_GROUP_MAX):
             part = idx[i0:i0 + _lib.GEMM_GROUP_MAX]
-            arr = (_lib.GemmArgs * len(part))()
-            keep = []
-            ws = _workspace(items[part[0]][0].device, 1)
-            for g, i in zip(arr, part):
-                dy, x, M, N, K, conv = items[i]
-                out = torch.empty((M, N), dtype=F32, device=dy.device)
+            arr, keep = _wgrad_group_args([items[i] for i in part], _workspace(items[part[0]][0].device, 1))
+            for i, out in zip(part, keep[0]):
                 outs[i] = out
-                g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), out.data_ptr()
-                g.M, g.N, g.K = M, N, K
-                g.lda, g.ldb, g.ldc = dy.stride(0), (N if conv is not None else x.stride(0)), out.stride(0)
-                g.trans_a, g.trans_b, g.out_f32, g.alpha = 1, 1, 1, 1.0
-                if conv is not None:
-                    cg = _lib.ConvGather(*conv)
-                    g.conv = C.pointer(cg)
-                    keep.append(cg)
-                g.workspace, g.workspace_bytes = ws.data_ptr(), WS_BYTES
             check(lib.ph_gemm_grouped_bf16(arr, len(part), _stream()), 'ph_gemm_grouped_bf16 (split wgrad)')
+    return outs
+
+
+def _wgrad_group_args(items, ws):
+    """ph_gemm_args of one group of wgrad_split_grouped items sharing the workspace ws -> (array, [fresh fp32 outputs, keep-alives])"""
+    arr = (_lib.GemmArgs * len(items))()
+    outs, keep = [], []
+    for g, (dy, x, M, N, K, conv) in zip(arr, items):
+        out = torch.empty((M, N), dtype=F32, device=dy.device)
+        outs.append(out)
+        g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), out.data_ptr()
+        g.M, g.N, g.K = M, N, K
+        g.lda, g.ldb, g.ldc = dy.stride(0), (N if conv is not None else x.stride(0)), out.stride(0)
+        g.trans_a, g.trans_b, g.out_f32, g.alpha = 1, 1, 1, 1.0
+        if conv is not None:
+            cg = _lib.ConvGather(*conv)
+            g.conv = C.pointer(cg)
+            keep.append(cg)
+        if ws is not None:
+            g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
+    return arr, [outs, keep]
+
+
+def conv_wgrad_persistent(items, ws=None):
+    """The conv weight gradients of ONE layer of several expert stems (items as in wgrad_split_grouped, all with a conv gather) in one launch
+    of the persistent 256x128 kernel: units of (problem, tile, k-range) fill its blocks evenly, cut tiles are folded inside the launch.
+    Returns the fp32 outputs, or None -- nothing launched -- when the library would not take that kernel for the group (ph_gemm_route: a
+    reduction that is no multiple of 64 or shorter than 32 k-tiles, ...): the caller then keeps its per-expert calls.
+    ws: fp32 scratch for counters and slabs, or None for the default below.
+    Default workspace: a buffer of its own (which = 2).  The launch is issued on the main stream while (a) the weight-gradient queue's grouped
+    launches may still be running on the side stream with ITS stream's which = 1 buffer and (b) the deferred split-K calls of the same layer
+    (first dense layer) have parked partial sums in THIS stream's which = 1 buffer until gemm_flush_deferred(); which = 0 belongs to
+    whatever split-K / LayerNorm call comes next.  Consecutive layers share the buffer: launches on one stream run one after the other,
+    and the counters are zeroed on the stream ahead of every launch."""
+    if not items or len(items) > _lib.GEMM_GROUP_MAX:
+        return None
+    if ws is None:
+        ws = _workspace(items[0][0].device, 2)
+    arr, (outs, keep) = _wgrad_group_args(items, ws)
+    info = _lib.GemmRouteInfo()
+    if lib.ph_gemm_route(arr, len(items), 1, 0, C.byref(info)) != 0 or info.part[0].cls != _lib.GEMM_CLS_BIG_GROUPED:
+        return None
+    check(lib.ph_gemm_grouped_bf16(arr, len(items), _stream()), 'ph_gemm_grouped_bf16 (stem conv wgrad)')
     return outs
 
 

@@ -25,6 +25,11 @@ BF16, F32 = torch.bfloat16, torch.float32
 # element (QuickGELU' / erf-GELU').
 SAVE_ACT_GRAD = True
 
+# The stems' 3x3-conv weight gradients: True = the experts' problems of a layer in ONE launch of the persistent k-balanced 256x128 kernel
+# (ops.conv_wgrad_persistent) wherever the library takes it; False = one deferred split-K call per expert everywhere (the earlier path,
+# kept for the A/B of tools/step_ab.py and tests/test_stem_wgrad_stems_gpu.py).
+STEM_WGRAD_GROUPED = True
+
 
 def _bwd_act(act):
     return ACT_SAVED_GRAD
@@ -304,13 +309,26 @@ class EncoderProgram:
                 dys.append(dy)
             ops.bn_relu_bwd_grouped(bn_items)
             dcol_probs, dcols = [], []
+            # the layer's implicit-GEMM weight gradients (C % 8 == 0) as ONE launch of the persistent k-balanced kernel where the library takes
+            # it (long reductions that are multiples of 64 pixels); the first dense layer (C = 1 / 3, explicit col0) and everything else
+            # keep the per-expert deferred split-K calls
+            grouped = {}
+            if STEM_WGRAD_GROUPED:
+                cand = [(dom, s, dy) for dom, s, dy in zip(doms, S, dys)
+                        if s['geo'][i][1] % 8 == 0 and P.g(f'conv1.{dom}.{1 + 3 * i}.weight') is not None]
+                outs = ops.conv_wgrad_persistent([(dy, s['a_in'][i].view(-1, s['geo'][i][1]), dy.shape[1], s['geo'][i][3], dy.shape[0],
+                                                   (s['B'], s['geo'][i][0], s['geo'][i][0], s['geo'][i][1], 3, s['geo'][i][2])) for _, s, dy in cand])
+                if outs is not None:
+                    grouped = {dom: ds for (dom, _, _), ds in zip(cand, outs)}
             for dom, s, dy in zip(doms, S, dys):
                 H, C, stride, Kp = s['geo'][i]
                 wname = f'conv1.{dom}.{1 + 3 * i}.weight'
                 g = P.g(wname)
                 Co = P.shape[wname][0]
                 if g is not None:
-                    if C % 8 == 0:                                 # implicit-GEMM weight gradient: the im2col view sits on the reduction side
+                    if dom in grouped:
+                        ds = grouped[dom]
+                    elif C % 8 == 0:                               # implicit-GEMM weight gradient: the im2col view sits on the reduction side
                         ds = ops.gemm(dy, s['a_in'][i].view(-1, C), trans_a=True, trans_b=True, out_f32=True, M=Co, N=Kp, K=dy.shape[0],
                                       conv=(s['B'], H, H, C, 3, stride), defer_reduce=True)
                     else:

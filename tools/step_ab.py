@@ -23,6 +23,10 @@ ARMS = {
     'attn_res': dict(attn_mode=1),
     'ln_old': dict(ln_mode=0),                   # ph_layernorm_tuning(0): one-row-per-wave LayerNorm kernels
     'ln_new': dict(ln_mode=1),
+    # the stems' conv weight gradients: one persistent k-balanced launch per layer / one deferred split-K call per expert
+    # (prismer_amd/programs/encoder.py STEM_WGRAD_GROUPED, read while the step is captured)
+    'stem_wgrad_grouped': dict(stem_wgrad=True),
+    'stem_wgrad_per_expert': dict(stem_wgrad=False),
 }
 
 
@@ -35,6 +39,11 @@ def make(arm):
     if 'attn_mode' in spec:
         _lib.lib.ph_attention_tuning(spec['attn_mode'])
     restore = []
+    if 'stem_wgrad' in spec:
+        from prismer_amd.programs import encoder as E
+        was = E.STEM_WGRAD_GROUPED
+        E.STEM_WGRAD_GROUPED = spec['stem_wgrad']
+        restore.append(lambda: setattr(E, 'STEM_WGRAD_GROUPED', was))
     extra = spec.get('trainer', {})
     if extra:
         from prismer_amd import trainer as T
