@@ -37,17 +37,53 @@ _WS = {}
 WS_BYTES = 256 << 20
 
 
-def _workspace(device, which=0):
-    """per-(device, stream) fp32 scratch for split-K partial tiles / LayerNorm partials: kernels on one stream are
-    serialised, so one buffer per stream is race-free (allocated once, reused by every launch on that stream).
-    which = 1: the separate buffer that holds the partial sums of DEFERRED fold passes until gemm_flush_deferred()
-    which = 2: counters and slabs of the stems' grouped conv weight gradients (conv_wgrad_persistent)"""
-    key = (device, _raw_stream(device.index if device.index is not None else _cur_device()), which)
+# roles of the three fp32 scratch buffers a (device, stream) owns
+WS_CALL, WS_DEFERRED, WS_STEM_WGRAD = 0, 1, 2
+
+
+def _workspace(device, role=WS_CALL):
+    """per-(device, stream, role) fp32 scratch, allocated once and reused by every launch on that stream.  Kernels on one stream are serialised,
+    so a buffer is race-free as long as nothing parks data in it across launches; the roles keep apart what does:
+      WS_CALL        split-K partial tiles / LayerNorm partials of a single call (gemm, layernorm_bwd): written and folded inside the call, so the
+                     next call on the stream may reuse it
+      WS_DEFERRED    partial sums that OUTLIVE their call: gemm(defer_reduce=True) parks them until gemm_flush_deferred(); also the grouped
+                     launches of the weight-gradient queue and of wgrad_split_grouped, which fold inside the launch or in a pass issued right
+                     behind it and park nothing -- on the main stream they may share the buffer with deferred folds only because no caller puts
+                     one between a deferred call and its flush (the stems flush per layer); the queue normally runs on the side stream, i.e. on
+                     that stream's own buffer
+      WS_STEM_WGRAD  counters and slabs of the stems' persistent launch (conv_wgrad_persistent): issued on the main stream while the deferred
+                     split-K calls of the same layer (first dense layer) have partial sums parked in this stream's WS_DEFERRED and whatever
+                     split-K / LayerNorm call comes next takes WS_CALL.  Consecutive layers share it: launches on one stream run one after the
+                     other and the counters are zeroed on the stream ahead of every launch"""
+    key = (device, _raw_stream(device.index if device.index is not None else _cur_device()), role)
     ws = _WS.get(key)
     if ws is None:
         ws = torch.empty(WS_BYTES // 4, dtype=F32, device=device)
         _WS[key] = ws
     return ws
+
+
+def _set_drop(s, drop):
+    """the dropout triple of an argument structure (zero-initialised = no dropout); True when dropout is on"""
+    if drop is None or drop.p <= 0.0:
+        return False
+    s.drop_p, s.drop_seed, s.drop_stream = drop.p, drop.seed.data_ptr(), drop.stream
+    return True
+
+
+def launch_grouped(entry, array_type, items, fill, group_max=_lib.GEMM_GROUP_MAX, what='', cut=None):
+    """items in launches of at most group_max: per launch one ctypes array, fill(arr, j, item) writes element j (what it returns stays referenced
+    until the launch is issued), entry(arr, n, stream) issues it.  cut(i0, i1) -> the end (<= i1) of the launch that starts at item i0, for a
+    grouping rule beyond the maximum."""
+    i0 = 0
+    while i0 < len(items):
+        i1 = min(i0 + group_max, len(items))
+        if cut is not None:
+            i1 = cut(i0, i1)
+        arr = (array_type * (i1 - i0))()
+        keep = [fill(arr, j, items[i]) for j, i in enumerate(range(i0, i1))]     # noqa: F841 -- alive across the call below
+        check(entry(arr, i1 - i0, _stream()), what)
+        i0 = i1
 
 
 class SideStream:
@@ -142,13 +178,6 @@ class WgradQueue:
 
     def __init__(self):
         self.enabled = True
-        # False: nothing is launched before flush() -- the grouped launches are big (hundreds of 16 us tiles); issued while the
-        # decoder's chain of small dependent kernels is running they take every CU slot and each chain kernel then waits for
-        # slots to drain.  True: launch as soon as 16 problems of one reduction length are queued.
-        self.eager_flush = False
-        # > 0 (with eager_flush): mid-segment launches are BACKGROUND launches of at most this many blocks (each walks several
-        # tiles), so the weight gradients trickle through the CUs the chain leaves idle; the flush at the segment end is uncapped
-        self.bg_blocks = 0
         self.gemms = {}          # K -> [(dy, x, gw, M, N, K)] (flush() appends the paired bias gradient, or None, as a 7th element)
         self.cols = []           # [(dy, gb, M, N)]
         self.folds = []          # [(dshadow, dw, Cout, Cin, ks, Kp)]  conv weight gradients: shadow layout -> parameter layout
@@ -170,18 +199,13 @@ class WgradQueue:
         if not self.enabled:
             gemm(dy, x, out=gw, trans_a=True, trans_b=True, out_f32=True, accumulate=True, M=M, N=N, K=K)
             return
-        q = self.gemms.setdefault(K, [])                           # (two writers of one output never share a launch: _flush_gemms)
-        q.append((dy, x, gw, M, N, K))
-        if self.eager_flush and len(q) == _lib.GEMM_GROUP_MAX:
-            self._flush_gemms(K, self.bg_blocks)
+        self.gemms.setdefault(K, []).append((dy, x, gw, M, N, K))  # (two writers of one output never share a launch: _flush_gemms)
 
     def add_colsum(self, dy, gb, N):
         if not self.enabled:
             colsum(dy, gb, N=N)
             return
         self.cols.append((dy, gb, dy.shape[0], N))
-        if self.eager_flush and len(self.cols) == _lib.GEMM_GROUP_MAX:
-            self._flush_cols()
 
     def add_conv_fold(self, ds, dw, Cout, Cin, ks, Kp):
         """dw[Cout, Cin, ks, ks] += ds[Cout, Kp] (im2col column order): queued behind the GEMM that produces ds on the
@@ -198,7 +222,7 @@ class WgradQueue:
         defer (queue off, arena full, or a stream other than the one the pending partials were written on)"""
         if not self.enabled:
             return None
-        cur = torch.cuda.current_stream().cuda_stream
+        cur = _stream()
         if self.lns and self.ln_stream != cur:
             return None
         n = blocks * 2 * D
@@ -216,45 +240,44 @@ class WgradQueue:
 
     def _flush_lns(self):
         q, self.lns, self.ln_off = self.lns, [], 0
-        for i0 in range(0, len(q), _lib.GEMM_GROUP_MAX):
-            part = q[i0:i0 + _lib.GEMM_GROUP_MAX]
-            arr = (_lib.LnReduceItem * len(part))()
-            for it, (ws, blocks, D, dg, db) in zip(arr, part):
-                it.ws, it.blocks, it.D, it.dgamma, it.dbeta = ws.data_ptr(), blocks, D, ptr(dg), ptr(db)
-            check(lib.ph_ln_param_reduce_grouped(arr, len(part), _stream()), 'ph_ln_param_reduce_grouped')
 
-    def _flush_gemms(self, K, max_blocks=0):
+        def fill(arr, j, e):
+            it, (ws, blocks, D, dg, db) = arr[j], e
+            it.ws, it.blocks, it.D, it.dgamma, it.dbeta = ws.data_ptr(), blocks, D, ptr(dg), ptr(db)
+        launch_grouped(lib.ph_ln_param_reduce_grouped, _lib.LnReduceItem, q, fill, what='ph_ln_param_reduce_grouped')
+
+    def _flush_gemms(self, K):
         allq = self.gemms.pop(K, [])
         if not allq:
             return
-
         excl = self.exclusive
 
+        def cut(i0, i1):                             # no output twice in one launch
+            seen = set()
+            for i in range(i0, i1):
+                if allq[i][2].data_ptr() in seen:
+                    return i
+                seen.add(allq[i][2].data_ptr())
+            return i1
+
+        def entry(arr, n, stream):
+            # the workspace is for the persistent kernel's k-balanced plan only (partial tiles folded inside the launch); a group
+            # that plan leaves whole is issued without one, as before
+            info = _lib.GemmRouteInfo()
+            if lib.ph_gemm_route(arr, n, 1, 0, C.byref(info)) != 0 or info.part[0].fold != _lib.GEMM_FOLD_IN_LAUNCH:
+                gemm_args_drop_workspace(arr)
+            return lib.ph_gemm_grouped_capped_bf16(arr, n, 0, stream)
+
         def work():
-            i0 = 0
-            while i0 < len(allq):                    # <= 16 problems per launch, no output twice in one launch
-                q, seen = [], set()
-                while i0 < len(allq) and len(q) < _lib.GEMM_GROUP_MAX and allq[i0][2].data_ptr() not in seen:
-                    seen.add(allq[i0][2].data_ptr()); q.append(allq[i0]); i0 += 1
-                arr = (_lib.GemmArgs * len(q))()
-                ws = _workspace(q[0][0].device, 1)
-                for g, (dy, x, gw, M, N, Kk, *gb) in zip(arr, q):
-                    g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), gw.data_ptr()
-                    g.a_colsum = ptr(gb[0]) if gb else None
-                    g.workspace, g.workspace_bytes = ws.data_ptr(), WS_BYTES
-                    g.M, g.N, g.K = M, N, Kk
-                    g.lda, g.ldb, g.ldc = dy.stride(0), x.stride(0), gw.stride(0)
-                    # single-writer outputs of the native step are OVERWRITTEN (no read of the zeroed buffer, and AdamW does not
-                    # have to zero it): self.exclusive is set by the Trainer for the duration of its own step only
-                    acc = 0 if (excl is not None and gw.data_ptr() in excl) else 1
-                    g.trans_a, g.trans_b, g.out_f32, g.accumulate, g.alpha = 1, 1, 1, acc, 1.0
-                # the workspace is for the persistent kernel's k-balanced plan only (partial tiles folded inside the launch); a group
-                # that plan leaves whole is issued without one, as before
-                info = _lib.GemmRouteInfo()
-                if max_blocks or lib.ph_gemm_route(arr, len(q), 1, 0, C.byref(info)) != 0 or info.part[0].fold != _lib.GEMM_FOLD_IN_LAUNCH:
-                    for g in arr:
-                        g.workspace, g.workspace_bytes = None, 0
-                check(lib.ph_gemm_grouped_capped_bf16(arr, len(q), max_blocks, _stream()), 'ph_gemm_grouped_capped_bf16')
+            ws = _workspace(allq[0][0].device, WS_DEFERRED)
+
+            def fill(arr, j, e):
+                dy, x, gw, M, N, Kk, *gb = e
+                # single-writer outputs of the native step are OVERWRITTEN (no read of the zeroed buffer, and AdamW does not
+                # have to zero it): self.exclusive is set by the Trainer for the duration of its own step only
+                gemm_args(dy, x, gw, M, N, Kk, trans_a=True, trans_b=True, out_f32=True, a_colsum=gb[0] if gb else None,
+                          accumulate=excl is None or gw.data_ptr() not in excl, workspace=ws, into=arr[j])
+            launch_grouped(entry, _lib.GemmArgs, allq, fill, what='ph_gemm_grouped_capped_bf16', cut=cut)
         off_critical_path(work, *[t for e in allq for t in e[:3]], *[e[6] for e in allq if len(e) > 6 and e[6] is not None])
 
     def _pair_cols(self):
@@ -282,13 +305,12 @@ class WgradQueue:
         if not allq:
             return
 
+        def fill(arr, j, e):
+            it, (dy, gb, M, N) = arr[j], e
+            it.x, it.out, it.M, it.N, it.ld = dy.data_ptr(), gb.data_ptr(), M, N, dy.stride(0)
+
         def work():
-            for i0 in range(0, len(allq), _lib.GEMM_GROUP_MAX):
-                q = allq[i0:i0 + _lib.GEMM_GROUP_MAX]
-                arr = (_lib.ColsumItem * len(q))()
-                for it, (dy, gb, M, N) in zip(arr, q):
-                    it.x, it.out, it.M, it.N, it.ld = dy.data_ptr(), gb.data_ptr(), M, N, dy.stride(0)
-                check(lib.ph_colsum_grouped_bf16(arr, len(q), _stream()), 'ph_colsum_grouped_bf16')
+            launch_grouped(lib.ph_colsum_grouped_bf16, _lib.ColsumItem, allq, fill, what='ph_colsum_grouped_bf16')
         off_critical_path(work, *[t for e in allq for t in e[:2]])
 
     def flush(self):
@@ -317,10 +339,77 @@ def wait_side():
         SIDE.wait()
 
 
-def gemm(a, b, out=None, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, pre_out=None, act_in=None,
-         residual=None, drop=None, out_f32=False, accumulate=False, alpha=1.0, split_k=0, M=None, N=None, K=None, pre_grad=False,
-         conv=None, col_stats=None, defer_reduce=False):
-    """out[M,N] = epi(alpha * opA . opB^T).  a: [M,K] (or [K,M] if trans_a), b: [N,K] (or [K,N] if trans_b)."""
+def gemm_args(a, b, out, M, N, K, *, trans_a=False, trans_b=False, bias=None, act=ACT_NONE, pre_out=None, pre_grad=False, act_in=None,
+              residual=None, drop=None, out_f32=False, accumulate=False, alpha=1.0, split_k=0, conv=None, col_stats=None, a_colsum=None,
+              b_offset=0, rowmap=None, workspace=None, defer_reduce=False, into=None):
+    """The ph_gemm_args of out[M,N] = epi(alpha * opA . opB^T), a: [M,K] (or [K,M] if trans_a), b: [N,K] (or [K,N] if trans_b) -- the one place
+    that writes the structure; launches nothing.  Returns (args, keep-alive: what the structure points to besides the tensors passed in).
+    conv: the ConvGather integers, (B, H, W, C, ks, stride) or all twelve -- the A (forward, dgrad) / B (wgrad: trans_a) operand is an im2col
+          view of an NHWC activation; the gathered side's leading dimension is the width of that view
+    b_offset: bytes added to b's address (a tap range of the dgrad shadow);  rowmap: (wo, mul, sub, add) output-row scatter of a dgrad class
+    workspace: fp32 tensor for split-K partial tiles / the k-balanced plan, or None
+    into: a zero-initialised element of a group's array to fill instead of a fresh structure
+    Only the fields that differ from the zero-initialised structure are written (the eager step is bound by host time)."""
+    g = _lib.GemmArgs() if into is None else into
+    g.A, g.B, g.C = a.data_ptr(), b.data_ptr() + b_offset, out.data_ptr()
+    g.M, g.N, g.K = M, N, K
+    g.lda, g.ldb, g.ldc = a.stride(0), b.stride(0), out.stride(0)
+    g.alpha = alpha
+    if trans_a:
+        g.trans_a = 1
+    if trans_b:
+        g.trans_b = 1
+    cg = None
+    if conv is not None:
+        cg = _lib.ConvGather(*conv)
+        g.conv = C.pointer(cg)
+        if trans_a:
+            g.ldb = N
+        else:
+            g.lda = K
+    if col_stats is not None:
+        g.col_stats = col_stats.data_ptr()
+    if a_colsum is not None:
+        g.a_colsum = a_colsum.data_ptr()
+    if bias is not None:
+        g.bias = bias.data_ptr()
+    if act:
+        g.act = act
+    if pre_out is not None:
+        g.pre_out = pre_out.data_ptr()
+    if pre_grad:
+        g.pre_grad = 1
+    if act_in is not None:
+        g.act_in, g.ld_act = act_in.data_ptr(), act_in.stride(0)
+    if residual is not None:
+        g.residual, g.ldr, g.residual_f32 = residual.data_ptr(), residual.stride(0), int(residual.dtype == F32)
+    if drop is not None:
+        _set_drop(g, drop)
+    if out_f32:
+        g.out_f32 = 1
+    if accumulate:
+        g.accumulate = 1
+    if split_k:
+        g.split_k = split_k
+    if rowmap is not None:
+        g.rowmap_wo, g.rowmap_mul, g.rowmap_sub, g.rowmap_add = rowmap
+    if workspace is not None:
+        g.workspace, g.workspace_bytes = workspace.data_ptr(), workspace.numel() * 4
+    if defer_reduce:
+        g.defer_reduce = 1
+    return g, cg
+
+
+def gemm_args_drop_workspace(arr):
+    """gemm_args' one companion: a built group is issued without its workspace after all (the route can only be asked about built arguments)"""
+    for g in arr:
+        g.workspace, g.workspace_bytes = None, 0
+
+
+def gemm(a, b, out=None, *, trans_a=False, trans_b=False, out_f32=False, M=None, N=None, K=None, defer_reduce=False, **epilogue):
+    """out[M,N] = epi(alpha * opA . opB^T).  a: [M,K] (or [K,M] if trans_a), b: [N,K] (or [K,N] if trans_b); epilogue: gemm_args' keywords.
+    defer_reduce: a split-K call leaves its fold pass to gemm_flush_deferred() (one grouped launch for up to 16 of them); the partial sums of
+    the queued calls are parked in WS_DEFERRED."""
     if M is None:
         M = a.shape[1] if trans_a else a.shape[0]
     if K is None:
@@ -329,38 +418,8 @@ def gemm(a, b, out=None, *, trans_a=False, trans_b=False, bias=None, act=ACT_NON
         N = b.shape[1] if trans_b else b.shape[0]
     if out is None:
         out = torch.empty((M, N), dtype=F32 if out_f32 else BF16, device=a.device)
-    g = _lib.GemmArgs()
-    g.A, g.B, g.C = a.data_ptr(), b.data_ptr(), out.data_ptr()
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = a.stride(0), b.stride(0), out.stride(0)
-    g.trans_a, g.trans_b = int(trans_a), int(trans_b)
-    cg = None
-    if conv is not None:                              # (B, H, W, C, ks, stride): the A (forward) / B (wgrad) operand is an im2col view
-        cg = _lib.ConvGather(*conv)
-        g.conv = C.pointer(cg)
-        if trans_a:
-            g.ldb = N
-        else:
-            g.lda = K
-    g.col_stats = ptr(col_stats)
-    g.bias = ptr(bias)
-    g.act = act
-    g.pre_out = ptr(pre_out)
-    g.pre_grad = int(pre_grad)
-    g.act_in = ptr(act_in)
-    g.ld_act = act_in.stride(0) if act_in is not None else 0
-    g.residual = ptr(residual)
-    g.residual_f32 = int(residual is not None and residual.dtype == F32)
-    g.ldr = residual.stride(0) if residual is not None else 0
-    if drop is not None and drop.p > 0.0:
-        g.drop_p, g.drop_seed, g.drop_stream = drop.p, drop.seed.data_ptr(), drop.stream
-    else:
-        g.drop_p, g.drop_seed, g.drop_stream = 0.0, None, 0
-    g.out_f32, g.accumulate, g.alpha, g.split_k = int(out_f32), int(accumulate), float(alpha), int(split_k)
-    # defer_reduce: a split-K call leaves its fold pass to gemm_flush_deferred() (one grouped launch for up to 16 of them); the partial
-    # sums of the queued calls live in their own workspace, which nothing else uses
-    ws = _workspace(a.device, 1 if defer_reduce else 0)
-    g.workspace, g.workspace_bytes, g.defer_reduce = ws.data_ptr(), WS_BYTES, int(defer_reduce)
+    g, keep = gemm_args(a, b, out, M, N, K, trans_a=trans_a, trans_b=trans_b, out_f32=out_f32, defer_reduce=defer_reduce,
+                        workspace=_workspace(a.device, WS_DEFERRED if defer_reduce else WS_CALL), **epilogue)
     check(lib.ph_gemm_bf16(C.byref(g), _stream()), 'ph_gemm_bf16')
     return out
 
@@ -394,13 +453,12 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, *, dy_map=IDENT, dy2=None, dy2_map=I
     a.dy, a.dy_map, a.dy2, a.dy2_map = dy.data_ptr(), dy_map, ptr(dy2), dy2_map
     a.x, a.mean, a.rstd, a.gamma = x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr()
     a.dskip, a.dx = ptr(dskip), dx.data_ptr()
-    if drop is not None and drop.p > 0.0:
+    if _set_drop(a, drop):
         if dx_drop is None:
             dx_drop = torch.empty((M, D), dtype=BF16, device=x.device)
-        a.dx_drop, a.drop_p, a.drop_seed, a.drop_stream = dx_drop.data_ptr(), drop.p, drop.seed.data_ptr(), drop.stream
+        a.dx_drop = dx_drop.data_ptr()
     else:
         dx_drop = None
-        a.dx_drop, a.drop_p, a.drop_seed, a.drop_stream = None, 0.0, None, 0
     a.dgamma, a.dbeta, a.M, a.D = ptr(dgamma), ptr(dbeta), M, D
     slot = None
     if dgamma is not None or dbeta is not None:
@@ -422,10 +480,7 @@ def _attn_args(q, k, v, o, B, H, Sq, Sk, dh, strides, scale, key_mask, causal, d
     f.scale = scale
     f.key_mask = ptr(key_mask)
     f.causal = int(causal)
-    if drop is not None and drop.p > 0.0:
-        f.drop_p, f.drop_seed, f.drop_stream = drop.p, drop.seed.data_ptr(), drop.stream
-    else:
-        f.drop_p, f.drop_seed, f.drop_stream = 0.0, None, 0
+    _set_drop(f, drop)
     f.lse = ptr(lse)
     return f
 
@@ -530,34 +585,23 @@ def inpaint_resize(label_map, table, Hout, Wout):
     return y
 
 
-def conv_gemm_args(x, geo, w_shadow, y, col_stats=None):
-    """GemmArgs of one implicit-GEMM forward convolution: y[B*Ho*Wo, Cout] = im2col(x) . w_shadow[Cout, Kp]^T.
-    x: NHWC bf16 activation, geo = (B, H, W, C, ks, stride).  Returns (args, keep-alive tuple)."""
-    B, H, W, Cc, ks, stride = geo
-    Ho, Wo = conv_out_size(H, ks, stride), conv_out_size(W, ks, stride)
-    g = _lib.GemmArgs()
-    cg = _lib.ConvGather(B, H, W, Cc, ks, stride)
-    g.A, g.B, g.C = x.data_ptr(), w_shadow.data_ptr(), y.data_ptr()
-    g.M, g.N, g.K = B * Ho * Wo, w_shadow.shape[0], w_shadow.shape[1]
-    g.lda, g.ldb, g.ldc = w_shadow.shape[1], w_shadow.stride(0), y.stride(0)
-    g.alpha = 1.0
-    g.conv = C.pointer(cg)
-    g.col_stats = ptr(col_stats)
-    return g, (cg, x, w_shadow, y, col_stats)
-
-
 def conv_fwd_grouped(items):
     """items: [(x, geo, w_shadow, y, col_stats)] -- the same-layer convolutions of several expert stems in ONE launch per
-    PH_GEMM_GROUP_MAX problems (vit.py:88-120: the stems are independent until their tokens are concatenated)."""
-    for i0 in range(0, len(items), _lib.GEMM_GROUP_MAX):
-        part = items[i0:i0 + _lib.GEMM_GROUP_MAX]
-        arr = (_lib.GemmArgs * len(part))()
-        keep = []
-        for i, it in enumerate(part):
-            g, k = conv_gemm_args(*it)
-            arr[i] = g
-            keep.append(k)
-        check(lib.ph_gemm_grouped_bf16(arr, len(part), _stream()), 'ph_gemm_grouped_bf16 (conv)')
+    PH_GEMM_GROUP_MAX problems (vit.py:88-120: the stems are independent until their tokens are concatenated).  Each is an implicit GEMM
+    y[B*Ho*Wo, Cout] = im2col(x) . w_shadow[Cout, Kp]^T with x the NHWC bf16 activation and geo = (B, H, W, C, ks, stride)."""
+    def fill(arr, j, it):
+        x, (B, H, W, Cc, ks, stride), w_shadow, y, col_stats = it
+        return gemm_args(x, w_shadow, y, B * conv_out_size(H, ks, stride) * conv_out_size(W, ks, stride), w_shadow.shape[0], w_shadow.shape[1],
+                         conv=it[1], col_stats=col_stats, into=arr[j])
+    launch_grouped(lib.ph_gemm_grouped_bf16, _lib.GemmArgs, items, fill, what='ph_gemm_grouped_bf16 (conv)')
+
+
+def _wgrad_problem(item, ws):
+    """one item of wgrad_split_grouped -> (ph_gemm_args, its fresh fp32 output, keep-alive)"""
+    dy, x, M, N, K, conv = item
+    out = torch.empty((M, N), dtype=F32, device=dy.device)
+    g, keep = gemm_args(dy, x, out, M, N, K, trans_a=True, trans_b=True, out_f32=True, conv=conv, workspace=ws)
+    return g, out, keep
 
 
 def wgrad_split_grouped(items):
@@ -567,35 +611,24 @@ def wgrad_split_grouped(items):
     view of the NHWC activation x (conv = (B, H, W, C, ks, stride): the gathered operand sits on the reduction side).
     Implicit and plain problems cannot share a launch, so they are grouped separately."""
     outs = [None] * len(items)
+
+    def fill(arr, j, i):
+        arr[j], outs[i], keep = _wgrad_problem(items[i], _workspace(items[i][0].device, WS_DEFERRED))
+        return keep
     for want_conv in (True, False):
-        idx = [i for i, it in enumerate(items) if (it[5] is not None) == want_conv]
-        for i0 in range(0, len(idx), _lib.GEMM_GROUP_MAX):
-            part = idx[i0:i0 + _lib.GEMM_GROUP_MAX]
-            arr, keep = _wgrad_group_args([items[i] for i in part], _workspace(items[part[0]][0].device, 1))
-            for i, out in zip(part, keep[0]):
-                outs[i] = out
-            check(lib.ph_gemm_grouped_bf16(arr, len(part), _stream()), 'ph_gemm_grouped_bf16 (split wgrad)')
+        launch_grouped(lib.ph_gemm_grouped_bf16, _lib.GemmArgs, [i for i, it in enumerate(items) if (it[5] is not None) == want_conv], fill,
+                       what='ph_gemm_grouped_bf16 (split wgrad)')
     return outs
 
 
-def _wgrad_group_args(items, ws):
-    """ph_gemm_args of one group of wgrad_split_grouped items sharing the workspace ws -> (array, [fresh fp32 outputs, keep-alives])"""
-    arr = (_lib.GemmArgs * len(items))()
-    outs, keep = [], []
-    for g, (dy, x, M, N, K, conv) in zip(arr, items):
-        out = torch.empty((M, N), dtype=F32, device=dy.device)
+def wgrad_group_args(items, ws):
+    """ph_gemm_args of ONE group of wgrad_split_grouped items sharing the workspace ws (or None) -> (array, fresh fp32 outputs, keep-alives)"""
+    arr, outs, keep = (_lib.GemmArgs * len(items))(), [], []
+    for j, it in enumerate(items):
+        arr[j], out, k = _wgrad_problem(it, ws)
         outs.append(out)
-        g.A, g.B, g.C = dy.data_ptr(), x.data_ptr(), out.data_ptr()
-        g.M, g.N, g.K = M, N, K
-        g.lda, g.ldb, g.ldc = dy.stride(0), (N if conv is not None else x.stride(0)), out.stride(0)
-        g.trans_a, g.trans_b, g.out_f32, g.alpha = 1, 1, 1, 1.0
-        if conv is not None:
-            cg = _lib.ConvGather(*conv)
-            g.conv = C.pointer(cg)
-            keep.append(cg)
-        if ws is not None:
-            g.workspace, g.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-    return arr, [outs, keep]
+        keep.append(k)
+    return arr, outs, keep
 
 
 def conv_wgrad_persistent(items, ws=None):
@@ -603,17 +636,12 @@ def conv_wgrad_persistent(items, ws=None):
     of the persistent 256x128 kernel: units of (problem, tile, k-range) fill its blocks evenly, cut tiles are folded inside the launch.
     Returns the fp32 outputs, or None -- nothing launched -- when the library would not take that kernel for the group (ph_gemm_route: a
     reduction that is no multiple of 64 or shorter than 32 k-tiles, ...): the caller then keeps its per-expert calls.
-    ws: fp32 scratch for counters and slabs, or None for the default below.
-    Default workspace: a buffer of its own (which = 2).  The launch is issued on the main stream while (a) the weight-gradient queue's grouped
-    launches may still be running on the side stream with ITS stream's which = 1 buffer and (b) the deferred split-K calls of the same layer
-    (first dense layer) have parked partial sums in THIS stream's which = 1 buffer until gemm_flush_deferred(); which = 0 belongs to
-    whatever split-K / LayerNorm call comes next.  Consecutive layers share the buffer: launches on one stream run one after the other,
-    and the counters are zeroed on the stream ahead of every launch."""
+    ws: fp32 scratch for counters and slabs, or None for this stream's WS_STEM_WGRAD (see _workspace)."""
     if not items or len(items) > _lib.GEMM_GROUP_MAX:
         return None
     if ws is None:
-        ws = _workspace(items[0][0].device, 2)
-    arr, (outs, keep) = _wgrad_group_args(items, ws)
+        ws = _workspace(items[0][0].device, WS_STEM_WGRAD)
+    arr, outs, keep = wgrad_group_args(items, ws)
     info = _lib.GemmRouteInfo()
     if lib.ph_gemm_route(arr, len(items), 1, 0, C.byref(info)) != 0 or info.part[0].cls != _lib.GEMM_CLS_BIG_GROUPED:
         return None
@@ -663,47 +691,34 @@ def bn_relu_bwd(da, y, gamma, beta, stats, dgamma, dbeta, sums=None):
     return dy
 
 
-def _bn_items(items):
-    out = []
-    for i0 in range(0, len(items), _lib.BN_GROUP_MAX):
-        part = items[i0:i0 + _lib.BN_GROUP_MAX]
-        arr = (_lib.BnItem * len(part))()
-        for it, d in zip(arr, part):
-            it.y, it.a, it.dy = d['y'].data_ptr(), d['a'].data_ptr(), ptr(d.get('dy'))
-            it.M, it.C = d['y'].shape[0], d['y'].shape[1]
-            it.gamma, it.beta = d['gamma'].data_ptr(), d['beta'].data_ptr()
-            it.running_mean, it.running_var = ptr(d.get('running_mean')), ptr(d.get('running_var'))
-            it.stats, it.sums = d['stats'].data_ptr(), d['sums'].data_ptr()
-            it.dgamma, it.dbeta = ptr(d.get('dgamma')), ptr(d.get('dbeta'))
-        out.append((arr, len(part)))
-    return out
+def _bn_fill(arr, j, d):
+    it = arr[j]
+    it.y, it.a, it.dy = d['y'].data_ptr(), d['a'].data_ptr(), ptr(d.get('dy'))
+    it.M, it.C = d['y'].shape[0], d['y'].shape[1]
+    it.gamma, it.beta = d['gamma'].data_ptr(), d['beta'].data_ptr()
+    it.running_mean, it.running_var = ptr(d.get('running_mean')), ptr(d.get('running_var'))
+    it.stats, it.sums = d['stats'].data_ptr(), d['sums'].data_ptr()
+    it.dgamma, it.dbeta = ptr(d.get('dgamma')), ptr(d.get('dbeta'))
 
 
 def bn_apply_relu_grouped(items, training, momentum=0.1, eps=1e-5):
     """items: dicts y [M,C] bf16 (conv output), a [M,C] bf16 (out: relu(bn(y))), gamma, beta, running_mean, running_var,
     stats [4,C] fp32 (out), sums [PH_COLSTAT_SLABS = 8][2][C] fp64 (column sums / sums of squares from the conv GEMM epilogue,
     ph_gemm_args.col_stats; unused in eval mode)"""
-    for arr, n in _bn_items(items):
-        check(lib.ph_bn_apply_relu_grouped(arr, n, momentum, eps, int(training), _stream()), 'ph_bn_apply_relu_grouped')
+    launch_grouped(lambda arr, n, stream: lib.ph_bn_apply_relu_grouped(arr, n, momentum, eps, int(training), stream), _lib.BnItem, items, _bn_fill,
+                   _lib.BN_GROUP_MAX, 'ph_bn_apply_relu_grouped')
 
 
 def bn_relu_bwd_grouped(items):
     """items: dicts y, a (= dA, gradient w.r.t. relu(bn(y))), dy (out), gamma, beta, stats [4,C], sums [2,C] ZEROED, dgamma, dbeta"""
-    for arr, n in _bn_items(items):
-        check(lib.ph_bn_relu_bwd_grouped(arr, n, _stream()), 'ph_bn_relu_bwd_grouped')
+    launch_grouped(lib.ph_bn_relu_bwd_grouped, _lib.BnItem, items, _bn_fill, _lib.BN_GROUP_MAX, 'ph_bn_relu_bwd_grouped')
 
 
 def gemm_grouped(problems, trans_a=False, trans_b=False):
     """problems: [(a, b, out, M, N, K)] plain bf16 GEMMs of one layout in grouped launches (out bf16, no epilogue)"""
-    for i0 in range(0, len(problems), _lib.GEMM_GROUP_MAX):
-        part = problems[i0:i0 + _lib.GEMM_GROUP_MAX]
-        arr = (_lib.GemmArgs * len(part))()
-        for g, (a, b, out, M, N, K) in zip(arr, part):
-            g.A, g.B, g.C = a.data_ptr(), b.data_ptr(), out.data_ptr()
-            g.M, g.N, g.K = M, N, K
-            g.lda, g.ldb, g.ldc = a.stride(0), b.stride(0), out.stride(0)
-            g.trans_a, g.trans_b, g.alpha = int(trans_a), int(trans_b), 1.0
-        check(lib.ph_gemm_grouped_bf16(arr, len(part), _stream()), 'ph_gemm_grouped_bf16')
+    def fill(arr, j, p):
+        gemm_args(*p, trans_a=trans_a, trans_b=trans_b, into=arr[j])
+    launch_grouped(lib.ph_gemm_grouped_bf16, _lib.GemmArgs, problems, fill, what='ph_gemm_grouped_bf16')
 
 
 def tokens_finalize(feat, pos, tokens, B, G, D, tok_per_batch, tok_off, inst=None, E=0, g=0, table=None, inst_emb=None):
@@ -735,10 +750,7 @@ def embed_args(ids, word, pos, typ, gamma, beta, eps, pad_id, out, xhat, rstd, d
     a.word, a.pos, a.type = word.data_ptr(), pos.data_ptr(), typ.data_ptr()
     a.gamma, a.beta, a.eps = gamma.data_ptr(), beta.data_ptr(), eps
     a.out, a.xhat, a.rstd = out.data_ptr(), ptr(xhat), ptr(rstd)
-    if drop is not None and drop.p > 0.0:
-        a.drop_p, a.drop_seed, a.drop_stream = drop.p, drop.seed.data_ptr(), drop.stream
-    else:
-        a.drop_p, a.drop_seed, a.drop_stream = 0.0, None, 0
+    _set_drop(a, drop)
     a.out_f32 = ptr(out_f32)
     return a
 
@@ -963,24 +975,20 @@ def conv_grad_from_shadow(dshadow, dw, Cout, Cin, ks, Kp):
 
 def conv_layout_grouped(items, to_shadow):
     """items: [(src, dst, Cout, Cin, ks, Kp)]; one launch per PH_CONV_GROUP_MAX layers."""
-    fn = lib.ph_conv_weight_to_shadow_grouped if to_shadow else lib.ph_conv_grad_from_shadow_grouped
-    for i0 in range(0, len(items), _lib.CONV_GROUP_MAX):
-        part = items[i0:i0 + _lib.CONV_GROUP_MAX]
-        arr = (_lib.ConvLayoutItem * len(part))()
-        for it, (src, dst, Co, Ci, ks, Kp) in zip(arr, part):
-            it.src, it.dst, it.Cout, it.Cin, it.ks, it.Kp = src.data_ptr(), dst.data_ptr(), Co, Ci, ks, Kp
-        check(fn(arr, len(part), _stream()), 'ph_conv_layout_grouped')
+    def fill(arr, j, e):
+        it, (src, dst, Co, Ci, ks, Kp) = arr[j], e
+        it.src, it.dst, it.Cout, it.Cin, it.ks, it.Kp = src.data_ptr(), dst.data_ptr(), Co, Ci, ks, Kp
+    launch_grouped(lib.ph_conv_weight_to_shadow_grouped if to_shadow else lib.ph_conv_grad_from_shadow_grouped, _lib.ConvLayoutItem, items, fill,
+                   _lib.CONV_GROUP_MAX, 'ph_conv_layout_grouped')
 
 
 def conv_dgrad_shadows(items):
     """items: [(w fp32 [Cout,Cin,3,3], dst bf16 [Cin, 9*Cout], Cout, Cin, stride)]: weight operands of the implicit data gradients,
     one launch per PH_CONV_GROUP_MAX layers (include/prismer_hip.h: ph_conv_dgrad_shadow_grouped)"""
-    for i0 in range(0, len(items), _lib.CONV_GROUP_MAX):
-        part = items[i0:i0 + _lib.CONV_GROUP_MAX]
-        arr = (_lib.ConvDgradItem * len(part))()
-        for it, (w, dst, Co, Ci, stride) in zip(arr, part):
-            it.w, it.dst, it.Cout, it.Cin, it.stride = w.data_ptr(), dst.data_ptr(), Co, Ci, stride
-        check(lib.ph_conv_dgrad_shadow_grouped(arr, len(part), _stream()), 'ph_conv_dgrad_shadow_grouped')
+    def fill(arr, j, e):
+        it, (w, dst, Co, Ci, stride) = arr[j], e
+        it.w, it.dst, it.Cout, it.Cin, it.stride = w.data_ptr(), dst.data_ptr(), Co, Ci, stride
+    launch_grouped(lib.ph_conv_dgrad_shadow_grouped, _lib.ConvDgradItem, items, fill, _lib.CONV_GROUP_MAX, 'ph_conv_dgrad_shadow_grouped')
 
 
 # parity classes of the input pixel of a stride-2, 3x3, pad-1 convolution: (py, px) -> (first tap, taps) in the dgrad shadow
@@ -993,7 +1001,7 @@ def conv_dgrad_grouped(items):
     items: [(dy [B*Ho*Wo, Cout] bf16, wd [Cin, 9*Cout] dgrad shadow, dx [B*H*W, Cin] bf16 out, (B, H, W, Cin, Cout, stride))].
     stride 1: dX = conv3x3(dY) with flipped taps, one problem.  stride 2: one problem per parity class of the input pixel: the
     A operand gathers a (1+py) x (1+px) window of dY, the output rows are scattered to the class's pixels (GemmArgs.rowmap_*)."""
-    probs, keep = [], []
+    probs = []
     for dy, wd, dx, (B, H, W, Ci, Co, stride) in items:
         Ho, Wo = (H, W) if stride == 1 else (H // 2, W // 2)
         if stride == 1:
@@ -1002,25 +1010,16 @@ def conv_dgrad_grouped(items):
             assert H % 2 == 0 and W % 2 == 0 and stride == 2
             classes = DGRAD_CLASSES
         for (py, px), t0, nt in classes:
-            g = _lib.GemmArgs()
             if stride == 1:
-                cg = _lib.ConvGather(B, Ho, Wo, Co, 3, 1, 3, 3, -1, -1, Ho, Wo)
+                conv, rowmap = (B, Ho, Wo, Co, 3, 1, 3, 3, -1, -1, Ho, Wo), None
             else:
-                cg = _lib.ConvGather(B, Ho, Wo, Co, 3, 1, 1 + py, 1 + px, 0, 0, Ho, Wo)
-                g.rowmap_wo, g.rowmap_mul, g.rowmap_sub, g.rowmap_add = Wo, 4, 2, py * W + px
-            g.A, g.B, g.C = dy.data_ptr(), wd.data_ptr() + 2 * t0 * Co, dx.data_ptr()
-            g.M, g.N, g.K = B * Ho * Wo, Ci, nt * Co
-            g.lda, g.ldb, g.ldc = nt * Co, wd.stride(0), dx.stride(0)
-            g.alpha = 1.0
-            g.conv = C.pointer(cg)
-            probs.append(g)
-            keep.append((cg, dy, wd, dx))
-    for i0 in range(0, len(probs), _lib.GEMM_GROUP_MAX):
-        part = probs[i0:i0 + _lib.GEMM_GROUP_MAX]
-        arr = (_lib.GemmArgs * len(part))()
-        for i, g in enumerate(part):
-            arr[i] = g
-        check(lib.ph_gemm_grouped_bf16(arr, len(part), _stream()), 'ph_gemm_grouped_bf16 (conv dgrad)')
+                conv, rowmap = (B, Ho, Wo, Co, 3, 1, 1 + py, 1 + px, 0, 0, Ho, Wo), (Wo, 4, 2, py * W + px)
+            # the class's taps are nt * Cout consecutive columns of the shadow's rows, from tap t0 on (bf16: 2 bytes)
+            probs.append(gemm_args(dy, wd, dx, B * Ho * Wo, Ci, nt * Co, conv=conv, rowmap=rowmap, b_offset=2 * t0 * Co))
+
+    def fill(arr, j, p):
+        arr[j] = p[0]
+    launch_grouped(lib.ph_gemm_grouped_bf16, _lib.GemmArgs, probs, fill, what='ph_gemm_grouped_bf16 (conv dgrad)')
 
 
 def add_i64(x, value=1):

@@ -13,8 +13,8 @@ overwrites it with dlogits.
 import torch
 
 from .. import ops
-from .._lib import ACT_GELU, ACT_RELU2
-from .encoder import LN, SAVE_ACT_GRAD, Linear, _bwd_act
+from .._lib import ACT_GELU, ACT_RELU2, ACT_SAVED_GRAD
+from .encoder import LN, Linear
 
 BF16, F32 = torch.bfloat16, torch.float32
 
@@ -161,7 +161,7 @@ class DecoderProgram:
 
     def adaptor_fwd(self, blk, h, hf, sv):
         dpre = torch.empty_like(h)
-        dact = blk['down'].fwd(h, act=ACT_RELU2, pre_out=dpre, pre_grad=SAVE_ACT_GRAD)
+        dact = blk['down'].fwd(h, act=ACT_RELU2, pre_out=dpre, pre_grad=True)
         s = blk['up'].fwd(dact, residual=hf, out_f32=True)
         y, yf, m, r = self.post_ln(blk['ln'], s)                          # norm_late (utils.py:61-62)
         if sv is not None:
@@ -170,7 +170,7 @@ class DecoderProgram:
 
     def adaptor_bwd(self, blk, s, dy):
         ds, _ = blk['ln'].bwd(dy, s['s'], s['m'], s['r'])
-        ddpre = blk['up'].dgrad(ds, act=_bwd_act(ACT_RELU2), act_in=s['dpre'])
+        ddpre = blk['up'].dgrad(ds, act=ACT_SAVED_GRAD, act_in=s['dpre'])
         blk['up'].wgrad(ds, s['dact'])
         blk['down'].wgrad(ddpre, s['h'])
         return blk['down'].dgrad(ddpre, residual=ds)
@@ -178,7 +178,7 @@ class DecoderProgram:
     def mlp_fwd(self, blk, li, h, hf, seed, sv):
         d = self.d
         ipre = torch.empty(h.shape[0], d.intermediate_size, dtype=BF16, device=h.device)
-        iact = blk['inter'].fwd(h, act=ACT_GELU, pre_out=ipre, pre_grad=SAVE_ACT_GRAD)
+        iact = blk['inter'].fwd(h, act=ACT_GELU, pre_out=ipre, pre_grad=True)
         dr_h = self.drop(li * 16 + 5, d.hidden_dropout_prob, seed)
         s = blk['out'].fwd(iact, drop=dr_h, residual=hf, out_f32=True)
         y, yf, m, r = self.post_ln(blk['ln'], s)
@@ -188,7 +188,7 @@ class DecoderProgram:
 
     def mlp_bwd(self, blk, s, dy):
         ds, dsd = blk['ln'].bwd(dy, s['s'], s['m'], s['r'], drop=s['dr_h'])
-        dipre = blk['out'].dgrad(dsd, act=_bwd_act(ACT_GELU), act_in=s['ipre'])
+        dipre = blk['out'].dgrad(dsd, act=ACT_SAVED_GRAD, act_in=s['ipre'])
         blk['out'].wgrad(dsd, s['iact'])
         blk['inter'].wgrad(dipre, s['h'])
         return blk['inter'].dgrad(dipre, residual=ds)

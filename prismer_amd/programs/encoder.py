@@ -10,6 +10,8 @@ reverse and writes weight gradients directly into the flat fp32 gradient buffer 
 Internal activation layout is batch-major [B*tokens, D] bf16; the [S, B, D] view the reference returns is a
 permuted view of the final buffer.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
@@ -20,19 +22,14 @@ from ..config import LABEL_DOMAINS
 BF16, F32 = torch.bfloat16, torch.float32
 
 
-# Activations inside a Linear: the forward epilogue stores act'(x) (bf16, taken from the fp32 accumulator) instead of x, and the
-# backward GEMM multiplies by it -- nothing in the backward needs x itself, and its epilogue loses two transcendentals per
-# element (QuickGELU' / erf-GELU').
-SAVE_ACT_GRAD = True
+# Activations inside a Linear: the forward epilogue stores act'(x) (bf16, taken from the fp32 accumulator) instead of x (pre_grad=True), and
+# the backward GEMM multiplies by it (act=ACT_SAVED_GRAD) -- nothing in the backward needs x itself, and its epilogue loses two
+# transcendentals per element (QuickGELU' / erf-GELU').
 
 # The stems' 3x3-conv weight gradients: True = the experts' problems of a layer in ONE launch of the persistent k-balanced 256x128 kernel
 # (ops.conv_wgrad_persistent) wherever the library takes it; False = one deferred split-K call per expert everywhere (the earlier path,
 # kept for the A/B of tools/step_ab.py and tests/test_stem_wgrad_stems_gpu.py).
 STEM_WGRAD_GROUPED = True
-
-
-def _bwd_act(act):
-    return ACT_SAVED_GRAD
 
 
 def _rup(x, m):
@@ -74,6 +71,18 @@ class Linear:
             ops.WQ.add_gemm(dy, x, gw, self.rows, self.cols, dy.shape[0])
         if gb is not None:
             ops.WQ.add_colsum(dy, gb, self.rows)
+
+
+class StemLayer(namedtuple('StemLayer', 'a_in y stats B H C Cout stride Kp wname col0')):
+    """what the backward needs of one 3x3 conv + BatchNorm + ReLU layer of one expert stem: the NHWC input a_in [B, H, H, C], the conv output
+    y [B*Ho*Ho, Cout], the BatchNorm stats [4, Cout], the geometry, the weight's name, and col0 -- the explicit im2col matrix [B*Ho*Ho, Kp] of a
+    first dense layer (C = 1 / 3), None where the convolution is an implicit GEMM"""
+    __slots__ = ()
+
+    @property
+    def conv(self):
+        """the conv gather (B, H, W, C, ks, stride) of the layer's implicit GEMMs"""
+        return (self.B, self.H, self.H, self.C, 3, self.stride)
 
 
 class LN:
@@ -227,8 +236,7 @@ class EncoderProgram:
             else:
                 inp = (val['label'] if name == 'obj_detection' else val).contiguous().float()
                 a = ops.resize_to_nhwc(inp, Hs, Hs)
-            st.append(dict(name=name, dom=dom, a=a, H=Hs, C=a.shape[3], B=a.shape[0], strides=(2, 2, 1, 1) if label else (2, 2, 2, 2),
-                           a_in=[], ys=[], stats=[], geo=[], col0=None))
+            st.append(dict(dom=dom, a=a, H=Hs, C=a.shape[3], B=a.shape[0], strides=(2, 2, 1, 1) if label else (2, 2, 2, 2), layers=[]))
         n_ch = sum(d.width // k for k in (8, 4, 2, 1))
         SL = COLSTAT_SLABS
         sums_arena = ops.zeros(len(st) * SL * 2 * n_ch, torch.float64, st[0]['a'].device) if st else None     # fp64: see tile_colstats
@@ -245,17 +253,17 @@ class EncoderProgram:
                 y = torch.empty(B * Ho * Ho, Co, dtype=BF16, device=e['a'].device)
                 sums = sums_arena[so:so + SL * 2 * Co].view(SL, 2, Co); so += SL * 2 * Co
                 stats = stats_arena[to:to + 4 * Co].view(4, Co); to += 4 * Co
+                col = None
                 if C % 8 == 0:
                     conv_items.append((e['a'], (B, H, H, C, 3, s_), shadow, y, sums if training else None))
                 else:                                              # Cin = 1 / 3: explicit im2col (K = 16 / 32), statistics still fused
                     col = ops.im2col(e['a'], B, H, H, C, 3, s_, Kp)
                     ops.gemm(col, shadow, out=y, col_stats=sums if training else None)
-                    e['col0'] = col
                 bn = self.mod.conv1[dom][2 + 3 * i]
                 a_next = torch.empty_like(y)
                 bn_items.append(dict(y=y, a=a_next, gamma=P.f(f'conv1.{dom}.{2 + 3 * i}.weight'), beta=P.f(f'conv1.{dom}.{2 + 3 * i}.bias'),
                                      running_mean=bn.running_mean, running_var=bn.running_var, stats=stats, sums=sums))
-                e['a_in'].append(e['a']); e['ys'].append(y); e['stats'].append(stats); e['geo'].append((H, C, s_, Kp))
+                e['layers'].append(StemLayer(e['a'], y, stats, B, H, C, Co, s_, Kp, wname, col))
                 e['a'], e['H'], e['C'] = a_next.view(B, Ho, Ho, Co), Ho, Co
             if conv_items:
                 ops.conv_fwd_grouped(conv_items)
@@ -270,7 +278,7 @@ class EncoderProgram:
             probs.append((a2, shadow, f, M, shadow.shape[0], Kp))
             feats.append(f)
             if sv is not None:
-                sv[e['dom']] = dict(a_in=e['a_in'], ys=e['ys'], stats=e['stats'], geo=e['geo'], a_last=a2, col0=e['col0'], B=e['B'], Hlast=e['H'])
+                sv[e['dom']] = dict(layers=e['layers'], a_last=a2, B=e['B'])
         if probs:
             ops.gemm_grouped(probs)
         return feats
@@ -297,47 +305,43 @@ class EncoderProgram:
         sums_arena = ops.zeros(len(doms) * 2 * n_ch, F32, dev)
         so = 0
         for i in (3, 2, 1, 0):
+            layers = [s['layers'][i] for s in S]
             bn_items, dys = [], []
-            for dom, s, da in zip(doms, S, das):
-                y = s['ys'][i]
-                Co = y.shape[1]
+            for dom, L, da in zip(doms, layers, das):
                 gname, bname = f'conv1.{dom}.{2 + 3 * i}.weight', f'conv1.{dom}.{2 + 3 * i}.bias'
-                dy = torch.empty_like(y)
-                bn_items.append(dict(y=y, a=da, dy=dy, gamma=P.f(gname), beta=P.f(bname), stats=s['stats'][i],
-                                     sums=sums_arena[so:so + 2 * Co], dgamma=P.g(gname), dbeta=P.g(bname)))
-                so += 2 * Co
+                dy = torch.empty_like(L.y)
+                bn_items.append(dict(y=L.y, a=da, dy=dy, gamma=P.f(gname), beta=P.f(bname), stats=L.stats,
+                                     sums=sums_arena[so:so + 2 * L.Cout], dgamma=P.g(gname), dbeta=P.g(bname)))
+                so += 2 * L.Cout
                 dys.append(dy)
             ops.bn_relu_bwd_grouped(bn_items)
-            dcol_probs, dcols = [], []
-            # the layer's implicit-GEMM weight gradients (C % 8 == 0) as ONE launch of the persistent k-balanced kernel where the library takes
-            # it (long reductions that are multiples of 64 pixels); the first dense layer (C = 1 / 3, explicit col0) and everything else
-            # keep the per-expert deferred split-K calls
+            # The layer's weight gradients, in shadow layout (folded into [Cout, Cin, 3, 3] with all other layers at the queue's flush), one of
+            #   persistent group       the experts' implicit GEMMs (C % 8 == 0) as ONE launch of the persistent k-balanced kernel, where the
+            #                          library takes it for the group (long reductions that are multiples of 64 pixels)
+            #   deferred implicit      per expert, a deferred split-K call with the im2col view on the reduction side
+            #   deferred explicit      per expert, the same call on col0 (first dense layer, C = 1 / 3)
             grouped = {}
             if STEM_WGRAD_GROUPED:
-                cand = [(dom, s, dy) for dom, s, dy in zip(doms, S, dys)
-                        if s['geo'][i][1] % 8 == 0 and P.g(f'conv1.{dom}.{1 + 3 * i}.weight') is not None]
-                outs = ops.conv_wgrad_persistent([(dy, s['a_in'][i].view(-1, s['geo'][i][1]), dy.shape[1], s['geo'][i][3], dy.shape[0],
-                                                   (s['B'], s['geo'][i][0], s['geo'][i][0], s['geo'][i][1], 3, s['geo'][i][2])) for _, s, dy in cand])
+                cand = [k for k, L in enumerate(layers) if L.col0 is None and P.g(L.wname) is not None]
+                outs = ops.conv_wgrad_persistent([(dys[k], layers[k].a_in.view(-1, layers[k].C), layers[k].Cout, layers[k].Kp, dys[k].shape[0],
+                                                   layers[k].conv) for k in cand])
                 if outs is not None:
-                    grouped = {dom: ds for (dom, _, _), ds in zip(cand, outs)}
-            for dom, s, dy in zip(doms, S, dys):
-                H, C, stride, Kp = s['geo'][i]
-                wname = f'conv1.{dom}.{1 + 3 * i}.weight'
-                g = P.g(wname)
-                Co = P.shape[wname][0]
+                    grouped = dict(zip(cand, outs))
+            dcol_probs, dcols = [], []
+            for k, (L, dy) in enumerate(zip(layers, dys)):
+                g = P.g(L.wname)
                 if g is not None:
-                    if dom in grouped:
-                        ds = grouped[dom]
-                    elif C % 8 == 0:                               # implicit-GEMM weight gradient: the im2col view sits on the reduction side
-                        ds = ops.gemm(dy, s['a_in'][i].view(-1, C), trans_a=True, trans_b=True, out_f32=True, M=Co, N=Kp, K=dy.shape[0],
-                                      conv=(s['B'], H, H, C, 3, stride), defer_reduce=True)
+                    if k in grouped:
+                        ds = grouped[k]
+                    elif L.col0 is None:
+                        ds = ops.gemm(dy, L.a_in.view(-1, L.C), trans_a=True, trans_b=True, out_f32=True, M=L.Cout, N=L.Kp, K=dy.shape[0],
+                                      conv=L.conv, defer_reduce=True)
                     else:
-                        ds = ops.gemm(dy, s['col0'], trans_a=True, trans_b=True, out_f32=True, M=Co, N=Kp, K=dy.shape[0],
-                                      defer_reduce=True)
-                    ops.WQ.add_conv_fold(ds, g, Co, C, 3, Kp)
+                        ds = ops.gemm(dy, L.col0, trans_a=True, trans_b=True, out_f32=True, M=L.Cout, N=L.Kp, K=dy.shape[0], defer_reduce=True)
+                    ops.WQ.add_conv_fold(ds, g, L.Cout, L.C, 3, L.Kp)
                 if i > 0:
-                    da = torch.empty(s['B'] * H * H, C, dtype=BF16, device=dev)
-                    dcol_probs.append((dy, self.conv_dgrad_shadow(wname, stride), da, (s['B'], H, H, C, Co, stride)))
+                    da = torch.empty(L.B * L.H * L.H, L.C, dtype=BF16, device=dev)
+                    dcol_probs.append((dy, self.conv_dgrad_shadow(L.wname, L.stride), da, (L.B, L.H, L.H, L.C, L.Cout, L.stride)))
                     dcols.append(da)
             ops.gemm_flush_deferred()                            # the split-K fold passes of this layer's weight gradients: one grouped launch
             if i > 0:
@@ -367,7 +371,7 @@ class EncoderProgram:
             lat1 = blk['out'].fwd(o, residual=lat)
             f, m3, r3 = blk['ln_ff'].fwd(lat1)
             hpre = torch.empty(B * L, 4 * W, dtype=BF16, device=xf.device)
-            hact = blk['fc'].fwd(f, act=ACT_RELU2, pre_out=hpre, pre_grad=SAVE_ACT_GRAD)
+            hact = blk['fc'].fwd(f, act=ACT_RELU2, pre_out=hpre, pre_grad=True)
             lat2 = blk['proj'].fwd(hact, residual=lat1)
             layers.append(dict(lat=lat, kvin=kvin, qin=qin, m1=m1, r1=r1, m2=m2, r2=r2, q=q, kv=kv, o=o, lse=lse, lat1=lat1, f=f,
                                m3=m3, r3=r3, hpre=hpre, hact=hact))
@@ -386,7 +390,7 @@ class EncoderProgram:
         xf = sv['xf']
         dxf = None
         for blk, s in zip(reversed(self.rblocks), reversed(sv['resampler'])):
-            dhpre = blk['proj'].dgrad(dlat, act=_bwd_act(ACT_RELU2), act_in=s['hpre'])
+            dhpre = blk['proj'].dgrad(dlat, act=ACT_SAVED_GRAD, act_in=s['hpre'])
             blk['proj'].wgrad(dlat, s['hact'])
             blk['fc'].wgrad(dhpre, s['f'])
             df = blk['fc'].dgrad(dhpre)
@@ -431,11 +435,11 @@ class EncoderProgram:
         x1 = blk['out'].fwd(o, residual=x)
         b_, m2, r2 = blk['aln'].fwd(x1)                                   # Adaptor, pre-norm (utils.py:63-64)
         dpre = torch.empty_like(b_)
-        dact = blk['down'].fwd(b_, act=ACT_RELU2, pre_out=dpre, pre_grad=SAVE_ACT_GRAD)
+        dact = blk['down'].fwd(b_, act=ACT_RELU2, pre_out=dpre, pre_grad=True)
         x2 = blk['up'].fwd(dact, residual=x1)
         c, m3, r3 = blk['ln_2'].fwd(x2)
         fpre = torch.empty(x.shape[0], 4 * W, dtype=BF16, device=x.device)
-        fact = blk['fc'].fwd(c, act=ACT_QUICKGELU, pre_out=fpre, pre_grad=SAVE_ACT_GRAD)
+        fact = blk['fc'].fwd(c, act=ACT_QUICKGELU, pre_out=fpre, pre_grad=True)
         x3 = blk['proj'].fwd(fact, residual=x2)
         if sv_list is not None:
             sv_list.append(dict(x=x, a=a, m1=m1, r1=r1, qkv=qkv, o=o, lse=lse, x1=x1, b=b_, m2=m2, r2=r2, dpre=dpre, dact=dact, x2=x2,
@@ -446,12 +450,12 @@ class EncoderProgram:
         d = self.d
         W, H = d.width, d.vit_heads
         dh = W // H
-        dfpre = blk['proj'].dgrad(dx3, act=_bwd_act(ACT_QUICKGELU), act_in=s['fpre'])
+        dfpre = blk['proj'].dgrad(dx3, act=ACT_SAVED_GRAD, act_in=s['fpre'])
         blk['proj'].wgrad(dx3, s['fact'])
         blk['fc'].wgrad(dfpre, s['c'])
         dc = blk['fc'].dgrad(dfpre)
         dx2, _ = blk['ln_2'].bwd(dc, s['x2'], s['m3'], s['r3'], dskip=dx3)
-        ddpre = blk['up'].dgrad(dx2, act=_bwd_act(ACT_RELU2), act_in=s['dpre'])
+        ddpre = blk['up'].dgrad(dx2, act=ACT_SAVED_GRAD, act_in=s['dpre'])
         blk['up'].wgrad(dx2, s['dact'])
         blk['down'].wgrad(ddpre, s['b'])
         db = blk['down'].dgrad(ddpre)

@@ -45,7 +45,7 @@ def item(Cout, conv, seed):
 
 
 def route_of(items, ws):
-    arr, keep = ops._wgrad_group_args(items, ws)
+    arr, *keep = ops.wgrad_group_args(items, ws)
     info = _lib.GemmRouteInfo()
     _lib.check(_lib.lib.ph_gemm_route(arr, len(items), 1, 0, C.byref(info)), 'ph_gemm_route')
     r = info.part[0]
@@ -53,7 +53,7 @@ def route_of(items, ws):
 
 
 def grouped_launch(items, ws):
-    arr, keep = ops._wgrad_group_args(items, ws)
+    arr, *keep = ops.wgrad_group_args(items, ws)
     stream = torch.cuda.current_stream().cuda_stream
     return lambda: _lib.check(_lib.lib.ph_gemm_grouped_bf16(arr, len(items), stream), 'ph_gemm_grouped_bf16'), keep
 
