@@ -32,7 +32,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* ABI revision: bumped whenever an argument struct or a signature changes (101: ph_conv_gather window fields, ph_gemm_args row map +
  * defer_reduce; 102: round 4; 103: round 5 -- ph_ce_fwd takes a row_loss scratch, no memset nodes anywhere; 104: round 6 -- ph_dense_minmax_partial,
- * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; 106: ph_gemm_route replaces ph_gemm_grouped_plan; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
+ * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; 106: ph_gemm_route replaces ph_gemm_grouped_plan; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_sample_step; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
 #define PH_VERSION 106
 
 enum { PH_OK = 0, PH_ERR_BAD_ARG = -1, PH_ERR_UNSUPPORTED = -2, PH_ERR_LAUNCH = -3 };
@@ -437,6 +437,46 @@ typedef struct {
   float len_div;
 } ph_beam_advance_args;
 int ph_beam_advance(const ph_beam_advance_args* args, hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Sampled decoding step (transformers generate(do_sample=True): MinLengthLogitsProcessor, TemperatureLogitsWarper, TopKLogitsWarper,
+ * TopPLogitsWarper, multinomial, and the bookkeeping of _sample).  The specification is
+ * prismer_amd/model/generate.py::sample_from_logits.
+ * ph_sample_step: one launch per decode step for all R = images * n rows.  Row r reads logit row r / rows_per_logit (1: a row of its own;
+ * n: one row per image, the first step after a per-image prefill).  Per row r that is not done, on its bf16 logits x read as fp32:
+ *   candidates   every finite column, but column eos_token_id when ban_eos != 0 (the host passes cur < min_length);
+ *   temperature  z = x / temperature;
+ *   top-k        (top_k > 0) candidates with z >= the top_k-th largest z stay, ties at that value ALL stay;
+ *   top-p        (top_p < 1) on the distribution over what top-k kept, by classes of equal logit: a class stays iff the mass of the strictly
+ *                higher classes is < top_p -- TopPLogitsWarper's rule, but a tie class at the boundary is kept whole where transformers cuts
+ *                inside it by sort order; the kept set is a threshold set {z >= tau};
+ *   draw         u = (w >> 8) * 2^-24, w = word 0 of philox4x32(counter = (r, cur, 0, 0x5a3b1e), key = seed) (csrc/common.h); inverse CDF
+ *                over the kept tokens in a DEFINED order: class descending, token id ascending inside a class; the token is the first one
+ *                whose cumulative kept mass exceeds u * Z_kept;
+ *   bookkeeping  ids[r][cur] = token; a row that draws EOS is done; a row without any candidate emits EOS and is done (seq_logprob
+ *                untouched); a done row emits pad_token_id and nothing else of its state changes;
+ *   seq_logprob[r] += log_softmax(x)[token] of the RAW row (temperature 1, no filter, the banned column included; NaN when the row holds a
+ *                NaN or +inf).
+ * Diagnostics (each nullable, one value per row): u_out the uniform; thr_out the lowest kept raw logit; kept_count_out; kept_mass_out the
+ * kept share of the post-top-k mass.  A done row or one without candidates reports thr +inf, count 0, mass 0.
+ * One 1024-thread block per row: a counting histogram of the 16-bit order-preserving bf16 key in LDS (integer atomics), fixed-order scans
+ * over it, a second sweep for the member of the chosen class.  No float atomics, no workspace: the same inputs give the same outputs.
+ * Masses are fp32 sums in a fixed order (relative error of the cumulative mass about 1e-5).
+ * Limits: 8 <= V <= 65535, ld >= V, ld % 8 == 0, logits 16-byte aligned, R >= 1, rows_per_logit >= 1 dividing R, 0 <= cur < Tmax,
+ * temperature > 0, 0 < top_p <= 1, top_k >= 0; else PH_ERR_BAD_ARG before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const void* logits; int64_t ld; /* bf16 [R / rows_per_logit][ld], V valid columns */
+  int V, R, rows_per_logit, Tmax, cur;
+  int64_t* ids;                   /* int64 [R][Tmax], column `cur` is written */
+  int32_t* done;                  /* int32 [R] */
+  float* seq_logprob;             /* fp32 [R] */
+  float temperature, top_p;
+  int top_k, eos_token_id, pad_token_id, ban_eos;
+  uint64_t seed;
+  float* u_out; float* thr_out; int32_t* kept_count_out; float* kept_mass_out;   /* [R] each, or NULL */
+} ph_sample_step_args;
+int ph_sample_step(const ph_sample_step_args* args, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer and small utilities.

@@ -163,6 +163,15 @@ class BeamAdvanceArgs(C.Structure):
                 ('pad_token_id', c_int), ('rows_rep', c_int), ('len_div', c_float)]
 
 
+class SampleStepArgs(C.Structure):
+    _fields_ = [('logits', c_void_p), ('ld', c_i64), ('V', c_int), ('R', c_int), ('rows_per_logit', c_int), ('Tmax', c_int), ('cur', c_int),
+                ('ids', c_void_p), ('done', c_void_p), ('seq_logprob', c_void_p),
+                ('temperature', c_float), ('top_p', c_float),
+                ('top_k', c_int), ('eos_token_id', c_int), ('pad_token_id', c_int), ('ban_eos', c_int),
+                ('seed', C.c_uint64),
+                ('u_out', c_void_p), ('thr_out', c_void_p), ('kept_count_out', c_void_p), ('kept_mass_out', c_void_p)]
+
+
 WS_BEAM_TOPK = 4         # PH_WS_BEAM_TOPK
 WS_GRAD_NORM = 5         # PH_WS_GRAD_NORM
 SQNORM_RANGES_MAX, SQNORM_BLOCKS_MAX = 4, 2048      # PH_SQNORM_RANGES_MAX, PH_SQNORM_BLOCKS_MAX
@@ -209,6 +218,7 @@ _SIGS = {
     'ph_softmax_gather_bf16': (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     'ph_beam_topk': (c_int, [C.POINTER(BeamTopkArgs), c_void_p]),
     'ph_beam_advance': (c_int, [C.POINTER(BeamAdvanceArgs), c_void_p]),
+    'ph_sample_step': (c_int, [C.POINTER(SampleStepArgs), c_void_p]),
     'ph_ce_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ph_ce_bwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'ph_adamw': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,

@@ -1,4 +1,4 @@
-"""Beam-search decoding for the caption / VQA heads.
+"""Beam-search and sampled decoding for the caption / VQA heads.
 
 Reference: `self.text_decoder.generate(input_ids=..., encoder_hidden_states=..., num_beams=3, max_length=..., min_length=...,
 length_penalty=...)` at model/prismer_caption.py:45-50 and model/prismer_vqa.py:52-58, i.e. transformers' (4.26.1)
@@ -30,6 +30,14 @@ Semantics kept from transformers 4.26.1 (num_return_sequences = 1, early_stoppin
   - an item is done when it holds num_beams hypotheses and the worst of them is at least best_running / cur_len ** length_penalty;
     done items are frozen (padding beams);
   - at max_length the running beams of unfinished items are added as hypotheses; the best hypothesis wins.
+
+Sampling (generate(do_sample=True), the second half of this file): `sample_from_logits` is the specification as tensor ops -- transformers'
+MinLengthLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial and the bookkeeping of _sample,
+with three things DEFINED that transformers leaves to its sort: top-p keeps whole classes of equal logit (the boundary tie class stays,
+so the kept set is a threshold set; transformers cuts inside it), the draw walks the kept tokens class descending / token id ascending,
+and the uniform of (seed, row, position) is a Philox word.  `sample_device` runs the step in the library (ops.sample_step, one launch per
+position); `sample` drives the decoder, the n rows of an image sharing its K/V and prompt as the beams do, with no re-ordering after
+the prompt's cache rows are handed out.
 """
 import torch
 
@@ -262,3 +270,219 @@ def beam_search(decoder, input_ids, attention_mask, enc, num_beams=3, max_length
         prog.decode_reorder(st, rows // nb if first[0] else rows)
         first[0] = False
     return beam_search_from_logits(step_tiled, input_ids, reorder_fn=reorder, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ sampled decoding
+PHILOX_ROUNDS = 7                                                  # PH_PHILOX_ROUNDS of csrc/common.h
+SAMPLE_MAX_V = 65535                                               # ph_sample_step: 16-bit class counts
+SAMPLE_MAX_GROUP = 8                                               # rows of one image the grouped decode step is used with (as the beams)
+
+
+def philox_word0(c0, c1, c2, c3, seed):
+    """word 0 of philox4x32(counter = (c0, c1, c2, c3), key = seed) of csrc/common.h, on python ints"""
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    for _ in range(PHILOX_ROUNDS):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c3 ^ k1) & 0xFFFFFFFF, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0
+
+
+def sample_uniforms(rows, cur, seed):
+    """fp32 [rows]: the uniform of every row at position cur, u = (w >> 8) * 2^-24 in [0, 1), a function of (seed, row, position) alone"""
+    return torch.tensor([(philox_word0(r, cur, 0, 0x5a3b1e, seed) >> 8) / 16777216.0 for r in range(rows)], dtype=torch.float32)
+
+
+def check_sampling_args(temperature=1.0, top_k=50, top_p=1.0, num_return_sequences=1):
+    if not (temperature > 0 and temperature < float('inf')):
+        raise ValueError(f'temperature must be a positive finite number, got {temperature}')
+    if not (0 < top_p <= 1):
+        raise ValueError(f'top_p must lie in (0, 1], got {top_p}')
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError(f'top_k must be an integer >= 0 (0 = off), got {top_k}')
+    if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+        raise ValueError(f'num_return_sequences must be an integer >= 1, got {num_return_sequences}')
+
+
+def sample_filter(x, temperature=1.0, top_k=50, top_p=1.0, banned_col=None):
+    """The kept set of every row of x (fp32 [R, V]: bf16 logits read as fp32) as (keep bool [R, V], z float64 [R, V] = x / temperature).
+    Candidates are the finite columns (a NaN is never one; -inf is what transformers' own filters write for a removed token; +inf has
+    no distribution) but `banned_col`.  Top-k keeps z >= the k-th largest z, ties included.  Top-p works on classes of equal logit over
+    what top-k kept: a class stays iff the mass of the strictly higher classes is < top_p, so the top class always stays and the kept set is
+    a threshold set -- TopPLogitsWarper's rule but inside the boundary class, which transformers cuts by sort position."""
+    x = x.float()
+    cand = torch.isfinite(x)
+    if banned_col is not None:
+        cand[:, banned_col] = False
+    z = x.double() / float(temperature)
+    ninf = torch.full_like(z, -float('inf'))
+    keep = cand
+    if top_k > 0:
+        zc = torch.where(cand, z, ninf)
+        kth = zc.topk(min(int(top_k), x.shape[1]), dim=1).values[:, -1:]
+        keep = cand & (zc >= kth)
+    if top_p < 1:
+        s, idx = torch.sort(torch.where(keep, z, ninf), dim=1, descending=True, stable=True)
+        live = torch.isfinite(s)
+        p = torch.where(live, torch.exp(s - s[:, :1]), torch.zeros_like(s))
+        p = p / p.sum(dim=1, keepdim=True).clamp_min(1e-300)
+        above = torch.cumsum(p, dim=1) - p                                        # mass before each sorted position ...
+        start = torch.ones_like(live)
+        start[:, 1:] = s[:, 1:] != s[:, :-1]
+        above = torch.where(start, above, torch.full_like(above, -1.0)).cummax(dim=1).values       # ... before the position's class
+        keep = torch.zeros_like(keep).scatter(1, idx, live & (above < top_p))
+    return keep, z
+
+
+def sample_draw(keep, z, u):
+    """token int64 [R] (-1 for a row that keeps nothing): inverse CDF over the kept tokens in the defined order -- class (logit)
+    descending, token id ascending inside a class -- the first token whose cumulative kept mass exceeds u * Z_kept; float64 masses."""
+    s, idx = torch.sort(torch.where(keep, z, torch.full_like(z, -float('inf'))), dim=1, descending=True, stable=True)
+    live = torch.isfinite(s)
+    mass = torch.where(live, torch.exp(s - s[:, :1]), torch.zeros_like(s))
+    C = torch.cumsum(mass, dim=1)
+    n_live = live.sum(dim=1)
+    hit = C > (u.double()[:, None] * C[:, -1:])
+    pos = torch.where(hit.any(dim=1), hit.int().argmax(dim=1), (n_live - 1).clamp_min(0))
+    tok = idx.gather(1, pos[:, None])[:, 0]
+    return torch.where(n_live > 0, tok, torch.full_like(tok, -1))
+
+
+def _trim_sampled(ids, T0, cur, eos_token_id):
+    """ids[:, :L], L = the longest row (EOS included) among positions < cur: what a loop that stops the moment every row is done returns"""
+    gen = ids[:, T0:cur].cpu() == eos_token_id
+    if gen.shape[1] == 0:
+        return ids[:, :cur]
+    first = torch.where(gen.any(dim=1), gen.int().argmax(dim=1) + 1, torch.full((gen.shape[0],), gen.shape[1]))
+    return ids[:, :T0 + int(first.max())]
+
+
+@torch.no_grad()
+def sample_from_logits(step_fn, input_ids, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50, top_p=1.0,
+                       eos_token_id=2, pad_token_id=1, seed=0, uniforms=None, reorder_fn=None):
+    """Sampled decoding as tensor ops: the SPECIFICATION of ph_sample_step / sample_device (transformers' generate(do_sample=True):
+    MinLengthLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial, bookkeeping of _sample).
+    step_fn(ids [B*n, T]) -> next-token logits for the last position, [B*n, V], or [B, V] when one row stands for the n rows of its
+    image (the first step after a per-image prefill); reorder_fn(rows int64 [B*n]) is then called once after that step with the
+    source row r // n of every row.  Row r = image * n + j.  Per step, on the logits rounded to bf16 and read as fp32:
+    `sample_filter` (EOS banned while cur < min_length), `sample_draw` with u = uniforms[r, cur] or `sample_uniforms`; a finished row
+    emits pad, a row that draws EOS is finished, a row without candidates emits EOS and is finished (its log-probability stays).
+    Returns (ids [B*n, L] padded with pad_token_id, L = the longest row, EOS included; seq_logprob fp32 [B*n] = the sum of
+    log_softmax(raw fp32 row)[token] over the drawn tokens: temperature 1, no filter, no ban)."""
+    check_sampling_args(temperature, top_k, top_p, num_return_sequences)
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    n, Tmax = int(num_return_sequences), max_length
+    R = B * n
+    ids = torch.full((R, max(Tmax, T0)), pad_token_id, dtype=torch.long, device=dev)
+    ids[:, :T0] = input_ids.repeat_interleave(n, dim=0)
+    done = torch.zeros(R, dtype=torch.bool, device=dev)
+    logprob = torch.zeros(R, dtype=torch.float32, device=dev)
+    cur = T0
+    while cur < Tmax and not bool(done.all()):
+        logits = step_fn(ids[:, :cur])
+        shared = logits.shape[0] != R
+        x = logits.bfloat16().float()
+        if shared:
+            x = x.repeat_interleave(n, dim=0)
+        keep, z = sample_filter(x, temperature, top_k, top_p, eos_token_id if cur < min_length else None)
+        u = (sample_uniforms(R, cur, seed) if uniforms is None else uniforms[:, cur].float().cpu()).to(dev)
+        tok = sample_draw(keep, z, u)
+        empty = tok < 0
+        tok = torch.where(empty, torch.full_like(tok, eos_token_id), tok)
+        lp = torch.log_softmax(x, dim=-1).gather(1, tok[:, None])[:, 0]
+        logprob = torch.where(done | empty, logprob, logprob + lp)
+        ids[:, cur] = torch.where(done, torch.full_like(tok, pad_token_id), tok)
+        done = done | (tok == eos_token_id)
+        if shared and reorder_fn is not None:
+            reorder_fn(torch.arange(R, device=dev) // n)
+        cur += 1
+    return _trim_sampled(ids, T0, cur, eos_token_id), logprob
+
+
+@torch.no_grad()
+def sample_device(step_fn, input_ids, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50, top_p=1.0,
+                  eos_token_id=2, pad_token_id=1, seed=0, reorder_fn=None, rows_rep=1):
+    """sample_from_logits with the step in the library (ops.sample_step: one launch per position for all rows) on state allocated once:
+    same arguments (no `uniforms`), same return value.  step_fn -> bf16 logits on the GPU; reorder_fn(rows int32 [rows_rep * B*n]) gets,
+    once, after a step whose logits had one row per image, l * B*n + r // n for l < rows_rep.  The one host read is the "all rows
+    done?" check every fourth step."""
+    from .. import ops
+    check_sampling_args(temperature, top_k, top_p, num_return_sequences)
+    B, T0 = input_ids.shape
+    dev = input_ids.device
+    n, Tmax = int(num_return_sequences), max_length
+    R = B * n
+    ids = torch.full((R, max(Tmax, T0)), pad_token_id, dtype=torch.long, device=dev)
+    ids[:, :T0] = input_ids.repeat_interleave(n, dim=0)
+    done = torch.zeros(R, dtype=torch.int32, device=dev)
+    logprob = torch.zeros(R, dtype=torch.float32, device=dev)
+    cur = T_start = T0
+    while cur < Tmax:
+        logits = step_fn(ids[:, :cur])
+        ops.sample_step(logits, ids, done, logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, cur < min_length, seed)
+        if logits.shape[0] != R and reorder_fn is not None:
+            i32 = torch.int32
+            rows = torch.arange(R, device=dev, dtype=i32) // n
+            reorder_fn((torch.arange(rows_rep, device=dev, dtype=i32)[:, None] * R + rows[None, :]).reshape(-1) if rows_rep > 1 else rows)
+        cur += 1
+        if (cur - T_start) % 4 == 0 and bool(done.cpu().all()):           # the one host read: R flags, every fourth step
+            break
+    return _trim_sampled(ids, T0, cur, eos_token_id), logprob
+
+
+def _device_sample_ok(device_sample, dev, V):
+    if device_sample is False:
+        return False
+    ok = dev.type == 'cuda' and 8 <= V <= SAMPLE_MAX_V
+    if device_sample and not ok:
+        raise ValueError(f'device_sample=True needs logits on the GPU and 8 <= vocabulary <= {SAMPLE_MAX_V}')
+    return ok
+
+
+@torch.no_grad()
+def sample(decoder, input_ids, attention_mask, enc, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50,
+           top_p=1.0, eos_token_id=2, pad_token_id=1, seed=0, use_cache=True, device_sample=None, share_image=True):
+    """Sampled decoding with the decoder, the counterpart of `beam_search`: n = num_return_sequences rows per image, row image * n + j.
+    Returns (ids [B*n, L], seq_logprob [B*n]) as `sample_from_logits` does.
+    device_sample: None = the device step (sample_device) when the logits are bf16 on the GPU and the vocabulary fits ph_sample_step,
+    else the tensor form; False forces the tensor form.
+    share_image: the n rows of an image share its cross-attention K/V (decode_begin(beams=n)), the prompt runs once per image and one
+    decode_reorder (source row r // n) hands the prompt's cache rows out; nothing is re-ordered afterwards.  n = 1 needs neither.  The
+    grouped decode step is used with up to SAMPLE_MAX_GROUP rows per image (what the beam search exercises); a larger n, or
+    share_image=False, tiles every image n times before anything runs."""
+    check_sampling_args(temperature, top_k, top_p, num_return_sequences)
+    B, T0 = input_ids.shape
+    n = int(num_return_sequences)
+    on_device = _device_sample_ok(device_sample, input_ids.device, decoder.config.vocab_size)
+    kw = dict(num_return_sequences=n, max_length=max_length, min_length=min_length, temperature=temperature, top_k=top_k, top_p=top_p,
+              eos_token_id=eos_token_id, pad_token_id=pad_token_id, seed=seed)
+    search = sample_device if on_device else sample_from_logits
+    att_b = torch.cat([attention_mask.repeat_interleave(n, dim=0), attention_mask.new_ones(B * n, max(max_length - T0, 0))], dim=1)
+    if not use_cache:
+        enc_b = enc.repeat_interleave(n, dim=0).contiguous()
+
+        def step(ids):
+            out = decoder(ids, attention_mask=att_b[:, :ids.shape[1]], encoder_hidden_states=enc_b, return_dict=True)
+            return out.logits[:, -1, :]
+        return search(step, input_ids, **kw)
+    if not share_image or n == 1 or n > SAMPLE_MAX_GROUP:
+        prog, enc_bf = decoder.decoding_program(enc.repeat_interleave(n, dim=0).contiguous() if n > 1 else enc)
+        st = prog.decode_begin(enc_bf, max_length)
+
+        def step(ids):
+            T = ids.shape[1]
+            return prog.decode(st, ids, att_b[:, :T], 0 if T == T0 else T - 1)
+        return search(step, input_ids, **kw)
+    prog, enc_bf = decoder.decoding_program(enc)
+    st = prog.decode_begin(enc_bf, max_length, beams=n)
+
+    def step(ids):
+        T = ids.shape[1]
+        if T == T0:                                                # the prompt once per image: the n rows of an image are identical here
+            return prog.decode(st, ids[::n], attention_mask, 0)
+        return prog.decode(st, ids, att_b[:, :T], T - 1)
+    kw['reorder_fn'] = lambda rows: prog.decode_reorder(st, rows)
+    if on_device:
+        kw['rows_rep'] = st['cache'][0].shape[0]
+    return search(step, input_ids, **kw)

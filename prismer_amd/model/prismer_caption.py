@@ -22,7 +22,9 @@ class PrismerCaption(Prismer):
         t = self._tokenize(text, return_tensors='pt', **kw).to(device)
         return t.input_ids, t.attention_mask
 
-    def forward(self, experts, caption=None, answer=None, train=True, prefix='', inference='generate', k_test=32, return_scores=False):
+    def forward(self, experts, caption=None, answer=None, train=True, prefix='', inference='generate', k_test=32, return_scores=False, sample=None):
+        """sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
+        num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences captions, image-major."""
         device = experts['rgb'].device
         pad = self.text_decoder.config.pad_token_id
         if train:
@@ -46,8 +48,12 @@ class PrismerCaption(Prismer):
                 else:
                     ids, att = self._ids(prefix, device)
                 ids, att = ids[:, :-1], att[:, :-1]                                        # drop </s>
-                outputs = self.text_decoder.generate(input_ids=ids, encoder_hidden_states=experts_train, attention_mask=att, num_beams=3,
-                                                     max_length=20, min_length=8)       # prismer_caption.py:45-50
+                if sample is None:
+                    outputs = self.text_decoder.generate(input_ids=ids, encoder_hidden_states=experts_train, attention_mask=att, num_beams=3,
+                                                         max_length=20, min_length=8)       # prismer_caption.py:45-50
+                else:
+                    outputs = self.text_decoder.generate(input_ids=ids, encoder_hidden_states=experts_train, attention_mask=att, do_sample=True,
+                                                         max_length=20, min_length=8, **sample)
                 if self.tokenizer is None:
                     return outputs
                 captions = []

@@ -847,6 +847,26 @@ def beam_advance(top, ids_in, ids_out, beam_scores, hyp_score, hyp_tok, hyp_len,
     check(lib.ph_beam_advance(C.byref(a), _stream()), 'ph_beam_advance')
 
 
+def sample_step(logits, ids, done, seq_logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, ban_eos, seed, diag=None):
+    """One sampled decoding step for every row (see ph_sample_step): over bf16 logit rows [R, V], or [R / n, V] when n consecutive rows share
+    one (a strided view is fine: row stride a multiple of 8 elements, rows 16-B aligned), it writes ids[:, cur] (int64 [R, Tmax]), done (int32 [R]) and seq_logprob (fp32 [R]) in place.
+    The draw of row r is a function of (seed, r, cur) alone.  diag: None or (u fp32, thr fp32, kept_count int32, kept_mass fp32), [R] each,
+    any of them None."""
+    assert logits.dim() == 2 and logits.dtype == BF16 and logits.stride(1) == 1
+    Rl, V = logits.shape
+    R = ids.shape[0]
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and R % Rl == 0 and ids.is_contiguous(), 'sample_step: ids int64 [R, Tmax], R a multiple of the logit rows'
+    assert done.dtype == torch.int32 and done.numel() == R and done.is_contiguous() and seq_logprob.dtype == F32 and seq_logprob.numel() == R \
+        and seq_logprob.is_contiguous()
+    d = [None] * 4 if diag is None else list(diag)
+    for t, dt in zip(d, (F32, F32, torch.int32, F32)):
+        assert t is None or (t.dtype == dt and t.numel() == R and t.is_contiguous())
+    a = _lib.SampleStepArgs(logits.data_ptr(), logits.stride(0), V, R, R // Rl, ids.shape[1], int(cur), ids.data_ptr(), done.data_ptr(), seq_logprob.data_ptr(),
+                            float(temperature), float(top_p), int(top_k), int(eos_token_id), int(pad_token_id), int(bool(ban_eos)),
+                            int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in d))
+    check(lib.ph_sample_step(C.byref(a), _stream()), 'ph_sample_step')
+
+
 def ce_bwd(logits, labels, B, T, V, eps, row_lse, dloss):
     check(lib.ph_ce_bwd(logits.data_ptr(), logits.stride(0), labels.data_ptr(), B, T, V, logits.shape[1], eps, row_lse.data_ptr(),
                         dloss.data_ptr(), _stream()), 'ph_ce_bwd')

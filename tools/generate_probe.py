@@ -9,7 +9,9 @@ namespaces) or is a copy / fill of the runtime as torch's, the rest as the libra
 ph_prof_collect's count of library ENTRY-POINT calls is printed beside it (some entry points launch two kernels).
 Prismer-BASE decoder with synthetic weights, random encoder states of the leg's length (S = (res / 16)^2 + 64 resampler latents).
     python tools/generate_probe.py [--reps N] [--out FILE]        all legs
-    python tools/generate_probe.py --profile [--arm new|parent]   one warm-up + one call of the first leg (for rocprofv3 --kernel-trace --stats)"""
+    python tools/generate_probe.py --profile [--arm new|parent]   one warm-up + one call of the first leg (for rocprofv3 --kernel-trace --stats)
+    python tools/generate_probe.py --sample [--reps N] [--out FILE]   sampled decoding (top_p 0.9, n = 1 and 5 per image, caption 480^2 B=32): the
+        tensor form (sample(device_sample=False)) against the device step (ph_sample_step), medians of alternating calls"""
 import argparse
 import ctypes as C
 import os
@@ -20,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from prismer_amd import _lib, config, synth
-from prismer_amd.model.generate import beam_search
+from prismer_amd.model.generate import beam_search, sample
 from prismer_amd.model.prismer import _Cfg
 from prismer_amd.modules.roberta import RobertaForCausalLMModified
 
@@ -88,8 +90,38 @@ def kernels_per_step(dec, d, enc, q, qa, leg, kw):
     return n_torch / steps, n_lib / steps, entry / steps
 
 
+def sample_arm(dec, d, reps, say):
+    """ms per sampled generate call, tensor form against device step, n = 1 and n = 5 rows per image"""
+    name, res, B, Tq, ragged, Tmax, Tmin, _ = LEGS[0]
+    enc, q, qa, S = inputs(d, B, Tq, ragged, res, 0)
+    say(f'sampled decoding, {name}, top_p 0.9, top_k 0, temperature 1: tensor = sample(device_sample=False), device = ph_sample_step')
+    say(f'{"n":>3s} {"arm":7s} {"ms/call median":>15s} {"half medians":>19s} {"steps":>6s}')
+    for n in (1, 5):
+        def run(kw, seed):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            with torch.no_grad():
+                ids, _ = sample(dec, q, qa, enc, num_return_sequences=n, max_length=Tmax, min_length=Tmin, top_k=0, top_p=0.9,
+                                eos_token_id=d.eos_token_id, pad_token_id=d.pad_token_id, seed=seed, **kw)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, ids.shape[1] - Tq
+        arms = [('tensor', dict(device_sample=False)), ('device', dict())]
+        for _, kw in arms:
+            run(kw, 0)                                                         # warm-up of both
+        times, steps = {a: [] for a, _ in arms}, {}
+        for i in range(reps):                                                  # alternating, the same seed for both arms of a round
+            for a, kw in arms:
+                ms, steps[a] = run(kw, 1 + i)
+                times[a].append(ms)
+        for a, _ in arms:
+            t = times[a]
+            say(f'{n:3d} {a:7s} {median(t):15.2f} {median(t[:len(t) // 2]):9.2f} {median(t[len(t) // 2:]):9.2f} {steps[a]:6d}')
+        say(f'{n:3d} tensor / device = {median(times["tensor"]) / median(times["device"]):.2f}x (medians)')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--sample', action='store_true')
     ap.add_argument('--reps', type=int, default=12)
     ap.add_argument('--out', default=None)
     ap.add_argument('--profile', action='store_true')
@@ -115,6 +147,14 @@ def main():
         return
     reps = max(args.reps, 10)
     props = torch.cuda.get_device_properties(0)
+    if args.sample:
+        say(f'device: {props.name}, {props.total_memory / 2**30:.0f} GiB; Prismer-BASE decoder (synthetic weights), random encoder states')
+        sample_arm(dec, d, reps, say)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+        return
     say(f'device: {props.name}, {props.total_memory / 2**30:.0f} GiB; Prismer-BASE decoder (synthetic weights), random encoder states, {NB} beams')
     say(f'parent = beam_search(device_beams=False, share_image=False): images tiled {NB}x, tensor-op beam step;  new = shared image K/V, device beam step')
     say(f'{"leg":20s} {"arm":7s} {"ms/call median":>15s} {"half medians":>19s} {"spread":>8s} {"peak added":>11s} {"kernels/step torch | library (entry calls)":>44s}')
