@@ -32,7 +32,7 @@ typedef struct ihipStream_t* hipStream_t;
 
 /* ABI revision: bumped whenever an argument struct or a signature changes (101: ph_conv_gather window fields, ph_gemm_args row map +
  * defer_reduce; 102: round 4; 103: round 5 -- ph_ce_fwd takes a row_loss scratch, no memset nodes anywhere; 104: round 6 -- ph_dense_minmax_partial,
- * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; 106: ph_gemm_route replaces ph_gemm_grouped_plan; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_sample_step; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
+ * ph_resize_remap_nchw_to_nhwc, ph_softmax_gather_bf16, new values of ph_gemm_tuning / ph_attention_tuning; 105: ph_store_words; 106: ph_gemm_route replaces ph_gemm_grouped_plan; additions that leave every existing struct and signature alone do not bump it: ph_beam_topk, ph_beam_advance, PH_WS_BEAM_TOPK; ph_sample_step; ph_beam_topk_edit, ph_sample_step_edit; ph_grad_sqnorm, ph_clip_finalize, ph_adamw_ctl, PH_WS_GRAD_NORM).  A host built against another revision must refuse to run: ph_version() != PH_VERSION. */
 #define PH_VERSION 106
 
 enum { PH_OK = 0, PH_ERR_BAD_ARG = -1, PH_ERR_UNSUPPORTED = -2, PH_ERR_LAUNCH = -3 };
@@ -416,6 +416,22 @@ typedef struct {
   int32_t* top_beam; int32_t* top_tok;   /* int32 [B][2*nb] */
 } ph_beam_topk_args;
 int ph_beam_topk(const ph_beam_topk_args* args, hipStream_t stream);
+/* ph_beam_topk_edit: ph_beam_topk with transformers' RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor applied to the
+ * log-probabilities before the beam score is added (the specification: prismer_amd/model/generate.py::decode_edits inside
+ * beam_search_from_logits).  ids int64 [B*nb][ids_ld], `cur` tokens per row: the whole row as transformers sees it, prompt and pad
+ * included.  The history of logit row q is ids row q * (nb / nb_in).  With l = logits[row][tok] - lse(row):
+ *   penalty   every token of the history scores beam_scores[row] + (l * theta if l < 0 else l / theta), theta = repetition_penalty, the
+ *             product and the IEEE quotient each rounded to fp32 before the add;
+ *   n-gram    n = no_repeat_ngram_size > 0, cur >= n: for every i in [0, cur - n] with ids[i : i+n-1] == ids[cur-n+1 : cur] column ids[i+n-1] is
+ *             no candidate (n = 1: every token of the history); a banned column wins over a penalised one.
+ * History tokens outside [0, V) are ignored (never used as an index).  Order and tie rule as ph_beam_topk; a banned column still counts in
+ * lse.  Same two launches: the first keeps the history columns out of each block's best (an LDS bitmap of the block's slice), the second
+ * scores the distinct history tokens one by one (at most cur gathers per row).  No atomics on floats, same outputs on every run.
+ * Limits: those of ph_beam_topk, ids non-null, 1 <= cur <= PH_EDIT_MAX_CUR, cur <= ids_ld, theta finite and > 0, n >= 0; else
+ * PH_ERR_BAD_ARG before any launch.  theta = 1 and n = 0 give ph_beam_topk's output. */
+#define PH_EDIT_MAX_CUR 512
+int ph_beam_topk_edit(const ph_beam_topk_args* args, const int64_t* ids, int64_t ids_ld, int cur, float repetition_penalty,
+                      int no_repeat_ngram_size, hipStream_t stream);
 /* ph_beam_advance: the bookkeeping of one step for all B items in one launch, from ph_beam_topk's output and the search state.  Per
  * item that is not done: the 2*nb candidates are visited in order until nb continuing beams are collected; an EOS candidate of rank < nb
  * becomes a hypothesis (score top_score / len_div, tokens = row of its beam with EOS at `cur`, length cur + 1; kept while fewer than nb
@@ -477,6 +493,15 @@ typedef struct {
   float* u_out; float* thr_out; int32_t* kept_count_out; float* kept_mass_out;   /* [R] each, or NULL */
 } ph_sample_step_args;
 int ph_sample_step(const ph_sample_step_args* args, hipStream_t stream);
+/* ph_sample_step_edit: ph_sample_step with the two processors applied to the row first (the specification: decode_edits inside
+ * sample_from_logits).  Row r's history is its own ids[r][0 : cur], whatever rows_per_logit is.  A token of the history has its logit
+ * replaced by bf16(x * theta if x < 0 else x / theta) (fp32 product / IEEE quotient, rounded to nearest even): the row is again a row of bf16
+ * logits, and candidates, classes, top-k, top-p and the draw are ph_sample_step's on it; an edited value that is not finite is no
+ * candidate.  A column the n-gram rule bans (as in ph_beam_topk_edit) is no candidate, like the banned EOS.  seq_logprob still adds the
+ * log-softmax of the RAW row at the drawn token; thr_out is an edited value.  A row whose candidates are all banned emits EOS and is done.
+ * Two LDS bitmaps (history, banned) of V bits beside the histogram; cur tokens of extra work per row, nothing V-wide; integer LDS atomics only.
+ * Limits: those of ph_sample_step, 1 <= cur <= PH_EDIT_MAX_CUR, theta finite and > 0, n >= 0; else PH_ERR_BAD_ARG before any launch. */
+int ph_sample_step_edit(const ph_sample_step_args* args, float repetition_penalty, int no_repeat_ngram_size, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Optimizer and small utilities.

@@ -174,6 +174,7 @@ class SampleStepArgs(C.Structure):
 
 WS_BEAM_TOPK = 4         # PH_WS_BEAM_TOPK
 WS_GRAD_NORM = 5         # PH_WS_GRAD_NORM
+EDIT_MAX_CUR = 512       # PH_EDIT_MAX_CUR
 SQNORM_RANGES_MAX, SQNORM_BLOCKS_MAX = 4, 2048      # PH_SQNORM_RANGES_MAX, PH_SQNORM_BLOCKS_MAX
 
 
@@ -219,6 +220,8 @@ _SIGS = {
     'ph_beam_topk': (c_int, [C.POINTER(BeamTopkArgs), c_void_p]),
     'ph_beam_advance': (c_int, [C.POINTER(BeamAdvanceArgs), c_void_p]),
     'ph_sample_step': (c_int, [C.POINTER(SampleStepArgs), c_void_p]),
+    'ph_beam_topk_edit': (c_int, [C.POINTER(BeamTopkArgs), c_void_p, c_i64, c_int, c_float, c_int, c_void_p]),
+    'ph_sample_step_edit': (c_int, [C.POINTER(SampleStepArgs), c_float, c_int, c_void_p]),
     'ph_ce_fwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ph_ce_bwd': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     'ph_adamw': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,

@@ -1,5 +1,6 @@
 // Beam-search step on the device (model/prismer_caption.py:45-50, model/prismer_vqa.py:52-58 run transformers' beam search: 3 beams).
 //   ph_beam_topk     log-softmax + beam score + EOS ban + the best 2*nb (beam, token) candidates of every image, in a DEFINED order
+//   ph_beam_topk_edit  the same with the repetition penalty and the n-gram ban applied to the log-probabilities of the history's tokens
 //   ph_beam_advance  the bookkeeping of one step (BeamSearchScorer.process + BeamHypotheses.add / is_done of transformers 4.26.1), the
 //                    device form of prismer_amd/model/generate.py::beam_search_from_logits
 #include <float.h>
@@ -7,6 +8,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "decode_edit.h"
 
 namespace {
 
@@ -35,15 +37,33 @@ __device__ __forceinline__ bool col_before(float xa, int ia, float xb, int ib) {
 // Stage 1: block (split, row) reads its share of the row ONCE (16-byte vectors, kept in registers), leaves (max, sum exp(x - max)) and
 // its K best (logit, column) pairs in the workspace record.  The K pairs come from K rounds of a block-wide arg-best over the
 // threads' cached best candidates; only the thread that owned the winner looks through its registers again.
+// EDIT (ph_beam_topk_edit): the columns of the row's history -- ids[row * hist_rep][0 : cur], every token the repetition penalty or
+// the n-gram rule can touch -- are marked in an LDS bitmap of the block's own slice and stay out of the K best (they still count in
+// max and sum); the merge kernel scores them one by one.  Work per block: cur tokens, nothing V-wide.
+template <bool EDIT>
 __global__ __launch_bounds__(BT_THREADS) void beam_topk_partial_kernel(const bf16* __restrict__ logits, int64_t ld, int V, int nsplit, int vec_per_split,
-                                                                       int K, int eos_banned, float* __restrict__ ws) {
+                                                                       int K, int eos_banned, float* __restrict__ ws, const int64_t* __restrict__ ids,
+                                                                       int64_t ids_ld, int cur, int hist_rep) {
   __shared__ float shf[2][BT_THREADS / 64];
   __shared__ int shi[2][BT_THREADS / 64];
+  __shared__ uint32_t hist_bits[EDIT ? BT_CHUNK_VEC * 8 / 32 : 1];
   const int row = blockIdx.y, split = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bf16* x = logits + (int64_t)row * ld;
   const int nvec = (V + 7) / 8;
   const int v0 = split * vec_per_split, v1 = min(v0 + vec_per_split, nvec);
+  if constexpr (EDIT) {
+    for (int i = tid; i < BT_CHUNK_VEC * 8 / 32; i += BT_THREADS) hist_bits[i] = 0;
+    __syncthreads();
+    const int64_t* h = ids + (int64_t)row * hist_rep * ids_ld;
+    const int64_t c0 = (int64_t)v0 * 8, c1 = min((int64_t)v1 * 8, (int64_t)V);
+    for (int t = tid; t < cur; t += BT_THREADS) {
+      const int64_t tok = h[t];
+      if (tok >= c0 && tok < c1) atomicOr(&hist_bits[(int)(tok - c0) >> 5], 1u << ((int)(tok - c0) & 31));
+    }
+    __syncthreads();
+  }
   float v[BT_NV][8];
+  uint32_t out_bits = 0;                               // EDIT: bit j * 8 + e = the thread's column (j, e) is a history token
   int col0[BT_NV];                                     // first column of the thread's j-th vector; V (= no valid column) when it has none
   float mx = -FLT_MAX;
 #pragma unroll
@@ -52,6 +72,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_topk_partial_kernel(const bf1
     if (c < v1) {
       const bf16x8 tv = *reinterpret_cast<const bf16x8*>(x + (int64_t)c * 8);
       col0[j] = c * 8;
+      if constexpr (EDIT) out_bits |= ((hist_bits[(c - v0) >> 2] >> (((c - v0) & 3) * 8)) & 0xFFu) << (j * 8);
 #pragma unroll
       for (int e = 0; e < 8; ++e) { v[j][e] = (c * 8 + e < V) ? bf2f(tv[e]) : -INFINITY; mx = fmaxf(mx, v[j][e]); }
     } else {
@@ -88,6 +109,7 @@ __global__ __launch_bounds__(BT_THREADS) void beam_topk_partial_kernel(const bf1
       for (int e = 0; e < 8; ++e) {
         const int col = col0[j] + e;
         const float xv = v[j][e];
+        if (EDIT && ((out_bits >> (j * 8 + e)) & 1u)) continue;
         if (col < V && col != eos_banned && col_before(lastx, lasti, xv, col) && col_before(xv, col, bx, bi)) { bx = xv; bi = col; }
       }
   };
@@ -125,9 +147,20 @@ __device__ __forceinline__ bool cand_before(const Cand& a, const Cand& b) {
 
 // Stage 2: one wave per image.  lse of each of its rows from the partial (max, sum) pairs, score = beam_score + (x - lse) for the
 // nb_in * nsplit * K surviving candidates, and K rounds of a wave-wide arg-best over them.
+// EDIT: the history tokens the partial kernel left out come back as explicit candidates.  Per row, every DISTINCT history token inside
+// [0, V) that the n-gram rule does not ban (and that is not the banned EOS) and whose logit is finite enters with
+// beam_score + edit(x - lse), edit(l) = l * theta if l < 0 else l / theta (RepetitionPenaltyLogitsProcessor on the log-probability),
+// x gathered from the logit row: at most cur gathers per row.  They live in dynamic LDS, nb_in * cur x (token, logit, score).
+struct BeamEdit {
+  const bf16* logits; int64_t ld; int V;
+  const int64_t* ids; int64_t ids_ld; int cur, hist_rep, ngram, eos_banned;
+  float theta;
+};
+template <bool EDIT>
 __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float* __restrict__ ws, const float* __restrict__ beam_scores, int nb_in, int nsplit, int K,
-                                                             float* __restrict__ top_score, int* __restrict__ top_beam, int* __restrict__ top_tok) {
+                                                             float* __restrict__ top_score, int* __restrict__ top_beam, int* __restrict__ top_tok, BeamEdit ed) {
   __shared__ float s_lse[8], s_bs[8];
+  extern __shared__ int edit_lds[];                    // EDIT: h_tok[cur], h_ban[cur], c_tok[nb_in * cur], c_x[..], c_s[..]
   const int b = blockIdx.x, lane = threadIdx.x;
   for (int r = 0; r < nb_in; ++r) {
     const float* rec = ws + (((int64_t)b * nb_in + r) * nsplit + lane) * BT_REC;
@@ -138,6 +171,52 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float* __rest
     if (lane == 0) { s_lse[r] = M + logf(tot); s_bs[r] = beam_scores[(int64_t)b * nb_in + r]; }
   }
   __syncthreads();
+  const int n_hist = EDIT ? nb_in * ed.cur : 0;
+  int* const h_tok = edit_lds;
+  int* const h_ban = h_tok + (EDIT ? ed.cur : 0);
+  int* const c_tok = h_ban + (EDIT ? ed.cur : 0);
+  float* const c_x = reinterpret_cast<float*>(c_tok + n_hist);
+  float* const c_s = c_x + n_hist;
+  if constexpr (EDIT) {
+    const int cur = ed.cur, ng = ed.ngram;
+    for (int r = 0; r < nb_in; ++r) {
+      const int64_t q = (int64_t)b * nb_in + r;
+      const int64_t* h = ed.ids + q * ed.hist_rep * ed.ids_ld;
+      // h_tok[t] = the token at t, -1 outside the vocabulary; h_ban[t] = the n-gram that ends at t starts like the row's last n - 1 tokens
+      for (int t = lane; t < cur; t += 64) {
+        const int64_t tok = h[t];
+        h_tok[t] = (tok >= 0 && tok < ed.V) ? (int)tok : -1;
+        int ban = 0;
+        if (ng > 0 && ng <= cur && t >= ng - 1) {
+          ban = 1;
+          for (int j = 0; j < ng - 1; ++j)
+            if (h[t - ng + 1 + j] != h[cur - ng + 1 + j]) { ban = 0; break; }
+        }
+        h_ban[t] = ban;
+      }
+      __syncthreads();
+      for (int t = lane; t < cur; t += 64) {
+        const int tok = h_tok[t];
+        bool ok = tok >= 0 && tok != ed.eos_banned;
+        for (int u = 0; ok && u < cur; ++u)
+          if (h_tok[u] == tok && (u < t || h_ban[u])) ok = false;      // an earlier copy stands for the token; a banned copy bans it
+        float x = 0.f, sc = 0.f;
+        if (ok) {
+          x = bf2f(ed.logits[q * ed.ld + tok]);
+          ok = fabsf(x) <= FLT_MAX;                    // finite: -inf is no candidate, a NaN never is
+          const float l = x - s_lse[r];
+          {
+#pragma clang fp contract(off)
+            sc = s_bs[r] + penalised(l, ed.theta);
+          }
+        }
+        c_tok[r * cur + t] = ok ? tok : -1;
+        c_x[r * cur + t] = x;
+        c_s[r * cur + t] = sc;
+      }
+      __syncthreads();
+    }
+  }
   const int per_row = nsplit * K, n = nb_in * per_row;
   const Cand none = {-INFINITY, INT_MAX, -INFINITY, INT_MAX};
   Cand last = {INFINITY, -1, INFINITY, -1}, best;
@@ -154,6 +233,12 @@ __global__ __launch_bounds__(64) void beam_topk_merge_kernel(const float* __rest
       c.s = s_bs[r] + (c.x - s_lse[r]);
       if (cand_before(last, c) && cand_before(c, best)) best = c;
     }
+    if constexpr (EDIT)
+      for (int i = lane; i < n_hist; i += 64) {
+        if (c_tok[i] < 0) continue;
+        const Cand c = {c_s[i], i / ed.cur, c_x[i], c_tok[i]};
+        if (cand_before(last, c) && cand_before(c, best)) best = c;
+      }
   };
   scan();
   for (int r = 0; r < K; ++r) {
@@ -244,7 +329,9 @@ int64_t beam_topk_workspace_bytes(int64_t B, int64_t nb, int64_t V) {
   return (one > all ? one : all) * BT_REC * 4;
 }
 
-extern "C" int ph_beam_topk(const ph_beam_topk_args* a, hipStream_t stream) {
+namespace {
+// the shared checks and launches of ph_beam_topk (ed == nullptr: the plain kernels) and ph_beam_topk_edit
+int beam_topk_launch(const ph_beam_topk_args* a, const BeamEdit* ed, hipStream_t stream) {
   PH_CHECK_ARG(a && a->logits && a->beam_scores && a->workspace && a->top_score && a->top_beam && a->top_tok, "ph_beam_topk: null pointer");
   PH_CHECK_ARG(a->nb >= 1 && a->nb <= 8, "ph_beam_topk: num_beams %d outside 1..8", a->nb);
   PH_CHECK_ARG(a->nb_in == 1 || a->nb_in == a->nb, "ph_beam_topk: nb_in %d must be 1 or num_beams %d", a->nb_in, a->nb);
@@ -260,12 +347,37 @@ extern "C" int ph_beam_topk(const ph_beam_topk_args* a, hipStream_t stream) {
                (long long)rows * nsplit * BT_REC * 4);
   const int nvec = (a->V + 7) / 8, vps = ceil_div(nvec, nsplit);
   ProfScope prof__(PH_FAM_MISC, 0.0, 2.0 * rows * (double)a->V, stream, "beam_topk");
-  hipLaunchKernelGGL(beam_topk_partial_kernel, dim3(nsplit, rows), dim3(BT_THREADS), 0, stream, (const bf16*)a->logits, a->ld, a->V, nsplit, vps, K,
-                     a->ban_eos ? a->eos_token_id : -1, (float*)a->workspace);
-  hipLaunchKernelGGL(beam_topk_merge_kernel, dim3(a->B), dim3(64), 0, stream, (const float*)a->workspace, a->beam_scores, a->nb_in, nsplit, K,
-                     a->top_score, a->top_beam, a->top_tok);
+  const int eos_banned = a->ban_eos ? a->eos_token_id : -1;
+  if (!ed) {
+    hipLaunchKernelGGL(beam_topk_partial_kernel<false>, dim3(nsplit, rows), dim3(BT_THREADS), 0, stream, (const bf16*)a->logits, a->ld, a->V, nsplit, vps,
+                       K, eos_banned, (float*)a->workspace, (const int64_t*)nullptr, (int64_t)0, 0, 0);
+    hipLaunchKernelGGL(beam_topk_merge_kernel<false>, dim3(a->B), dim3(64), 0, stream, (const float*)a->workspace, a->beam_scores, a->nb_in, nsplit, K,
+                       a->top_score, a->top_beam, a->top_tok, BeamEdit{});
+  } else {
+    BeamEdit e = *ed;
+    e.logits = (const bf16*)a->logits; e.ld = a->ld; e.V = a->V; e.hist_rep = a->nb / a->nb_in; e.eos_banned = eos_banned;
+    hipLaunchKernelGGL(beam_topk_partial_kernel<true>, dim3(nsplit, rows), dim3(BT_THREADS), 0, stream, e.logits, a->ld, a->V, nsplit, vps, K, eos_banned,
+                       (float*)a->workspace, e.ids, e.ids_ld, e.cur, e.hist_rep);
+    hipLaunchKernelGGL(beam_topk_merge_kernel<true>, dim3(a->B), dim3(64), (size_t)(2 + 3 * a->nb_in) * e.cur * 4, stream, (const float*)a->workspace,
+                       a->beam_scores, a->nb_in, nsplit, K, a->top_score, a->top_beam, a->top_tok, e);
+  }
   PH_LAUNCH_CHECK("beam_topk kernels");
   return PH_OK;
+}
+}  // namespace
+
+extern "C" int ph_beam_topk(const ph_beam_topk_args* a, hipStream_t stream) { return beam_topk_launch(a, nullptr, stream); }
+
+extern "C" int ph_beam_topk_edit(const ph_beam_topk_args* a, const int64_t* ids, int64_t ids_ld, int cur, float repetition_penalty, int no_repeat_ngram_size,
+                                 hipStream_t stream) {
+  PH_CHECK_ARG(ids, "ph_beam_topk_edit: null ids");
+  PH_CHECK_ARG(cur >= 1 && cur <= PH_EDIT_MAX_CUR && ids_ld >= cur, "ph_beam_topk_edit: history length %d outside 1..%d (row stride %lld)", cur, PH_EDIT_MAX_CUR,
+               (long long)ids_ld);
+  PH_CHECK_ARG(repetition_penalty > 0.f && repetition_penalty < INFINITY, "ph_beam_topk_edit: repetition_penalty must be a positive finite number");
+  PH_CHECK_ARG(no_repeat_ngram_size >= 0, "ph_beam_topk_edit: no_repeat_ngram_size %d below 0", no_repeat_ngram_size);
+  BeamEdit e{};
+  e.ids = ids; e.ids_ld = ids_ld; e.cur = cur; e.ngram = no_repeat_ngram_size; e.theta = repetition_penalty;
+  return beam_topk_launch(a, &e, stream);
 }
 
 extern "C" int ph_beam_advance(const ph_beam_advance_args* a, hipStream_t stream) {

@@ -2,6 +2,7 @@
 // TopKLogitsWarper, TopPLogitsWarper, multinomial, and the bookkeeping of _sample), the device form of
 // prismer_amd/model/generate.py::sample_from_logits.
 //   ph_sample_step   one launch per decode step: filters, draws and does the step's bookkeeping for every row
+//   ph_sample_step_edit   the same on the row after the repetition penalty (rounded back to bf16) and the n-gram ban
 //
 // One 1024-thread block per row.  bf16 logits take at most 65536 distinct values, so a counting histogram over the 16-bit
 // order-preserving key IS the sorted distribution: packed 16-bit counts (V <= 65535: no carry) in 128 KB of LDS, filled by integer LDS
@@ -14,6 +15,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "decode_edit.h"
 
 namespace {
 
@@ -107,11 +109,26 @@ __device__ __forceinline__ void walk_bins(const uint32_t* hist, int chunk, F fn)
   }
 }
 
-__global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_args a) {
+// bf16 bits of a history token's logit after the repetition penalty: fp32 product / IEEE quotient, rounded to nearest even
+__device__ __forceinline__ uint32_t edit_bits(uint32_t b, float theta) {
+  return (uint32_t)__builtin_bit_cast(unsigned short, f2bf(penalised(__uint_as_float(b << 16), theta)));
+}
+
+constexpr int SP_BITS = 65536 / 32;                    // words of a one-bit-per-column map
+
+// EDIT (ph_sample_step_edit): two more LDS maps, one bit per column -- `seen` (the column is a token of the row's history
+// ids[r][0 : cur]) and `ban` (the n-gram rule bans it) -- filled from the <= 512 history tokens, one per thread, before sweep 1.  A seen
+// column enters the histogram under the key of its penalised bf16 value, a banned one is left out like the banned EOS, and sweep 2 applies
+// the same transform.  The raw row's log-sum-exp needs the RAW histogram: each distinct history token has one owner thread (the one
+// whose atomicOr set the bit) that moves its count from the edited to the raw bin (banned tokens: adds it) with integer LDS atomics
+// before the raw sum is walked and moves it back afterwards, so that sum is over exact counts, in the plain kernel's order.
+template <bool EDIT>
+__global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_args a, float theta, int ngram) {
   __shared__ uint32_t hist[SP_PHYS];
+  __shared__ uint32_t seen_bits[EDIT ? SP_BITS : 1], ban_bits[EDIT ? SP_BITS : 1];
   __shared__ Scratch sc;
   __shared__ int s_bad, s_kth, s_cnt_ge, s_kept_cnt, s_hit, s_hit_j, s_tok;
-  __shared__ float s_eos_x, s_kept_mass;
+  __shared__ float s_eos_x, s_kept_mass, s_raw_x;
   const int r = blockIdx.x, tid = threadIdx.x;
   const int V = a.V, cur = a.cur;
   const int64_t out_i = (int64_t)r * a.Tmax + cur;
@@ -131,25 +148,74 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
   }
 
   for (int i = tid; i < SP_PHYS; i += SP_THREADS) hist[i] = 0;
-  if (tid == 0) { s_bad = 0; s_eos_x = -INFINITY; s_kth = 0; s_hit_j = 0; s_tok = a.eos_token_id; }
+  if constexpr (EDIT)
+    for (int i = tid; i < SP_BITS; i += SP_THREADS) { seen_bits[i] = 0; ban_bits[i] = 0; }
+  if (tid == 0) { s_bad = 0; s_eos_x = -INFINITY; s_kth = 0; s_hit_j = 0; s_tok = a.eos_token_id; s_raw_x = 0.f; }
   __syncthreads();
 
-  // ---- sweep 1: the histogram of the candidates (finite, not the banned EOS column)
   const bf16* x = reinterpret_cast<const bf16*>(a.logits) + (int64_t)(r / a.rows_per_logit) * a.ld;
   const int nvec = (V + 7) >> 3;                        // ld >= V and ld % 8 == 0: the last vector lies inside the row
   const int banned = a.ban_eos ? a.eos_token_id : -1;
+
+  // ---- EDIT: the history maps; thread t < cur takes history token t (cur <= 512)
+  int own_kr = -1, own_ke = -1;                        // the owner's raw key (the token's raw logit is finite) / edited key (it is in the histogram)
+  if constexpr (EDIT) {
+    const int64_t* h = a.ids + (int64_t)r * a.Tmax;
+    int e_tok = -1;
+    bool own = false;
+    if (tid < cur) {
+      const int64_t tok = h[tid];
+      if (tok >= 0 && tok < V) {                        // a token outside the vocabulary is never an index
+        e_tok = (int)tok;
+        own = !((atomicOr(&seen_bits[e_tok >> 5], 1u << (e_tok & 31)) >> (e_tok & 31)) & 1u);
+        if (ngram > 0 && ngram <= cur && tid >= ngram - 1) {
+          bool ban = true;
+          for (int j = 0; j < ngram - 1; ++j)
+            if (h[tid - ngram + 1 + j] != h[cur - ngram + 1 + j]) { ban = false; break; }
+          if (ban) atomicOr(&ban_bits[e_tok >> 5], 1u << (e_tok & 31));
+        }
+      }
+    }
+    __syncthreads();
+    if (own && e_tok != banned) {
+      const uint32_t rb = reinterpret_cast<const unsigned short*>(x)[e_tok];
+      if (bits_finite(rb)) {
+        own_kr = (int)key_of(rb);
+        const uint32_t eb = edit_bits(rb, theta);
+        if (!((ban_bits[e_tok >> 5] >> (e_tok & 31)) & 1u) && bits_finite(eb)) own_ke = (int)key_of(eb);
+      }
+    }
+  }
+  // moves the owners' counts from the edited bins to the raw bins (dir = 1) or back (dir = 0): integer adds, any order gives the same words
+  auto move_owned = [&](int dir) {
+    const int from = dir ? own_ke : own_kr, to = dir ? own_kr : own_ke;
+    if (from >= 0) atomicSub(&hist[(from >> 1) + (from >> 6)], 1u << ((from & 1) * 16));
+    if (to >= 0) atomicAdd(&hist[(to >> 1) + (to >> 6)], 1u << ((to & 1) * 16));
+  };
+
+  // ---- sweep 1: the histogram of the candidates (finite, not the banned EOS column)
   for (int c = tid; c < nvec; c += SP_THREADS) {
     const u32x4 tv = *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8);
+    uint32_t seen8 = 0, ban8 = 0;                      // EDIT: the vector's 8 bits of the two maps
+    if constexpr (EDIT) {
+      seen8 = (seen_bits[c >> 2] >> ((c & 3) * 8)) & 0xFFu;
+      if (seen8) ban8 = (ban_bits[c >> 2] >> ((c & 3) * 8)) & 0xFFu;
+    }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int col = c * 8 + e;
-      const uint32_t b = (tv[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
+      uint32_t b = (tv[e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
       if (col >= V) continue;
       if (!bits_finite(b)) {                           // NaN / +-inf: never a candidate; NaN or +inf spoil the row's log-softmax
         if (b != 0xFF80u) s_bad = 1;
         continue;
       }
       if (col == banned) { s_eos_x = __uint_as_float(b << 16); continue; }
+      if (EDIT && ((seen8 >> e) & 1u)) {
+        if ((ban8 >> e) & 1u) continue;
+        b = edit_bits(b, theta);
+        if (!bits_finite(b)) continue;                 // the penalised value overflowed bf16: no candidate
+      }
       const uint32_t key = key_of(b), wd = key >> 1;
       atomicAdd(&hist[wd + (wd >> 5)], 1u << ((key & 1u) * 16));
     }
@@ -198,18 +264,30 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
   const float T = a.temperature;
   const float mz = val_of(top_key) / T;
   const float eos_x = s_eos_x;
-  const float mr = fmaxf(val_of(top_key), eos_x);
+  float mr = fmaxf(val_of(top_key), eos_x);
   float mass_t = 0.f, raw_t = 0.f;
   if (n_t > 0)
     walk_bins(hist, chunk, [&](int key, int cnt) {
       const float xv = val_of(key);
-      raw_t += (float)cnt * __expf(xv - mr);
+      if (!EDIT) raw_t += (float)cnt * __expf(xv - mr);
       if (key >= kth) mass_t += (float)cnt * __expf(xv / T - mz);
       return true;
     });
   float Zk, raw_sum;
   const float A_t = block_scan_f(mass_t, sc, Zk);      // mass of the classes above this thread's bins
+  if constexpr (EDIT) {                                // the raw sum over the RAW histogram (every thread is past its walk: the scan's barriers)
+    move_owned(1);
+    __syncthreads();
+    int rtop_t = -1;
+    walk_bins(hist, chunk, [&](int key, int) { rtop_t = key; return false; });
+    mr = fmaxf(val_of(block_max_i(rtop_t, sc)), eos_x);          // N > 0: the raw row has a finite column
+    walk_bins(hist, chunk, [&](int key, int cnt) { raw_t += (float)cnt * __expf(val_of(key) - mr); return true; });
+  }
   (void)block_scan_f(raw_t, sc, raw_sum);
+  if constexpr (EDIT) {
+    move_owned(0);
+    __syncthreads();
+  }
   raw_sum += __expf(eos_x - mr);                       // 0 when no column is banned
   const float lse = mr + logf(raw_sum);
 
@@ -268,6 +346,17 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
   const int hit = s_hit, j = s_hit_j;
 
   // ---- sweep 2: the j-th column of the chosen class in ascending token order; thread t holds columns [t * per, (t + 1) * per)
+  // the histogram key column `col` went under in sweep 1, -1 if it was no candidate
+  auto member_key = [&](uint32_t b, uint32_t seen, uint32_t ban) -> int {
+    if (!bits_finite(b)) return -1;
+    if (EDIT && seen) {
+      if (ban) return -1;
+      b = edit_bits(b, theta);
+      if (!bits_finite(b)) return -1;
+    }
+    return (int)key_of(b);
+  };
+  auto map8 = [&](const uint32_t* bits, int c) -> uint32_t { return EDIT ? (bits[c >> 2] >> ((c & 3) * 8)) & 0xFFu : 0u; };
   const int vpt = (nvec + SP_THREADS - 1) / SP_THREADS;
   u32x4 tv[SP_MAX_VEC];
   int c_t = 0;
@@ -276,11 +365,11 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
     const int c = tid * vpt + i;
     if (i < vpt && c < nvec) {
       tv[i] = *reinterpret_cast<const u32x4*>(x + (int64_t)c * 8);
+      const uint32_t seen8 = map8(seen_bits, c), ban8 = map8(ban_bits, c);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const int col = c * 8 + e;
-        const uint32_t b = (tv[i][e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
-        if (col < V && col != banned && bits_finite(b) && (int)key_of(b) == hit) ++c_t;
+        if (col < V && col != banned && member_key((tv[i][e >> 1] >> ((e & 1) * 16)) & 0xFFFFu, (seen8 >> e) & 1u, (ban8 >> e) & 1u) == hit) ++c_t;
       }
     }
   }
@@ -292,12 +381,13 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
     for (int i = 0; i < SP_MAX_VEC; ++i) {
       const int c = tid * vpt + i;
       if (i < vpt && c < nvec) {
+        const uint32_t seen8 = map8(seen_bits, c), ban8 = map8(ban_bits, c);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const int col = c * 8 + e;
           const uint32_t b = (tv[i][e >> 1] >> ((e & 1) * 16)) & 0xFFFFu;
-          if (col < V && col != banned && bits_finite(b) && (int)key_of(b) == hit) {
-            if (left == 0 && tok < 0) tok = col;
+          if (col < V && col != banned && member_key(b, (seen8 >> e) & 1u, (ban8 >> e) & 1u) == hit) {
+            if (left == 0 && tok < 0) { tok = col; s_raw_x = __uint_as_float(b << 16); }
             --left;
           }
         }
@@ -311,7 +401,7 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
     const int tok = s_tok;
     a.ids[out_i] = tok;
     if (tok == a.eos_token_id) a.done[r] = 1;
-    a.seq_logprob[r] += s_bad ? NAN : (val_of(hit) - lse);
+    a.seq_logprob[r] += s_bad ? NAN : ((EDIT ? s_raw_x : val_of(hit)) - lse);
     if (a.u_out) a.u_out[r] = u;
     if (a.thr_out) a.thr_out[r] = val_of(L);
     if (a.kept_count_out) a.kept_count_out[r] = s_kept_cnt;
@@ -321,7 +411,9 @@ __global__ __launch_bounds__(SP_THREADS) void sample_step_kernel(ph_sample_step_
 
 }  // namespace
 
-extern "C" int ph_sample_step(const ph_sample_step_args* a, hipStream_t stream) {
+namespace {
+// the shared checks and the launch of ph_sample_step (edit = false) and ph_sample_step_edit
+int sample_step_launch(const ph_sample_step_args* a, bool edit, float theta, int ngram, hipStream_t stream) {
   PH_CHECK_ARG(a && a->logits && a->ids && a->done && a->seq_logprob, "ph_sample_step: null pointer");
   PH_CHECK_ARG(a->V >= 8 && a->V <= 65535, "ph_sample_step: vocabulary %d outside 8..65535 (16-bit class counts)", a->V);
   PH_CHECK_ARG(a->ld >= a->V && (a->ld % 8) == 0 && (((uintptr_t)a->logits) & 15) == 0,
@@ -333,8 +425,24 @@ extern "C" int ph_sample_step(const ph_sample_step_args* a, hipStream_t stream) 
   PH_CHECK_ARG(a->top_p > 0.f && a->top_p <= 1.f, "ph_sample_step: top_p outside (0, 1]");
   PH_CHECK_ARG(a->top_k >= 0, "ph_sample_step: top_k %d below 0", a->top_k);
   PH_CHECK_ARG(!a->ban_eos || (a->eos_token_id >= 0 && a->eos_token_id < a->V), "ph_sample_step: eos_token_id %d outside the vocabulary", a->eos_token_id);
+  if (edit) {
+    PH_CHECK_ARG(a->cur >= 1 && a->cur <= PH_EDIT_MAX_CUR, "ph_sample_step_edit: history length %d outside 1..%d", a->cur, PH_EDIT_MAX_CUR);
+    PH_CHECK_ARG(theta > 0.f && theta < INFINITY, "ph_sample_step_edit: repetition_penalty must be a positive finite number");
+    PH_CHECK_ARG(ngram >= 0, "ph_sample_step_edit: no_repeat_ngram_size %d below 0", ngram);
+  }
   ProfScope prof__(PH_FAM_MISC, 0.0, 4.0 * a->R * (double)a->V, stream, "sample_step");
-  hipLaunchKernelGGL(sample_step_kernel, dim3(a->R), dim3(SP_THREADS), 0, stream, *a);
+  if (!edit) {
+    hipLaunchKernelGGL(sample_step_kernel<false>, dim3(a->R), dim3(SP_THREADS), 0, stream, *a, 1.0f, 0);
+  } else {
+    hipLaunchKernelGGL(sample_step_kernel<true>, dim3(a->R), dim3(SP_THREADS), 0, stream, *a, theta, ngram);
+  }
   PH_LAUNCH_CHECK("sample_step_kernel");
   return PH_OK;
+}
+}  // namespace
+
+extern "C" int ph_sample_step(const ph_sample_step_args* a, hipStream_t stream) { return sample_step_launch(a, false, 1.0f, 0, stream); }
+
+extern "C" int ph_sample_step_edit(const ph_sample_step_args* a, float repetition_penalty, int no_repeat_ngram_size, hipStream_t stream) {
+  return sample_step_launch(a, true, repetition_penalty, no_repeat_ngram_size, stream);
 }

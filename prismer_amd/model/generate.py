@@ -38,10 +38,62 @@ so the kept set is a threshold set; transformers cuts inside it), the draw walks
 and the uniform of (seed, row, position) is a Philox word.  `sample_device` runs the step in the library (ops.sample_step, one launch per
 position); `sample` drives the decoder, the n rows of an image sharing its K/V and prompt as the beams do, with no re-ordering after
 the prompt's cache rows are handed out.
+
+repetition_penalty / no_repeat_ngram_size (both modes): `decode_edits` is transformers' RepetitionPenaltyLogitsProcessor and
+NoRepeatNGramLogitsProcessor as tensor ops, applied where transformers applies them -- to the log-probabilities before the beam score is
+added, to the raw logits before the sampling warpers.  On the device the step stays one library call (ph_beam_topk_edit,
+ph_sample_step_edit); with both options off every function here does exactly what it did without them.
 """
 import torch
 
 NEG = -1e9
+
+
+EDIT_MAX_CUR = 512                                                 # PH_EDIT_MAX_CUR: history length of ph_beam_topk_edit / ph_sample_step_edit
+
+
+def check_edit_args(repetition_penalty=1.0, no_repeat_ngram_size=0):
+    """transformers' conditions: RepetitionPenaltyLogitsProcessor wants a strictly positive float (finite here: inf and nan have no
+    meaning as a divisor), NoRepeatNGramLogitsProcessor an integer (0 = off)"""
+    t, n = repetition_penalty, no_repeat_ngram_size
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0 and t < float('inf')):
+        raise ValueError(f'repetition_penalty must be a finite float > 0, got {t}')
+    if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or n < 0:
+        raise ValueError(f'no_repeat_ngram_size must be an integer >= 0, got {n}')
+
+
+def _edits_on(repetition_penalty, no_repeat_ngram_size):
+    check_edit_args(repetition_penalty, no_repeat_ngram_size)
+    return float(repetition_penalty) != 1.0 or int(no_repeat_ngram_size) > 0
+
+
+def decode_edits(ids, x, repetition_penalty=1.0, no_repeat_ngram_size=0):
+    """transformers' RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor as tensor ops: the SPECIFICATION of
+    ph_beam_topk_edit / ph_sample_step_edit.  ids int64 [R, cur]: the whole row as transformers sees it (prompt and pad tokens count, no
+    attention mask is consulted); x [R, V] scores.  Returns (y [R, V], banned bool [R, V]); y is fp32 (float64 for a float64 x).
+      penalty  for every column t that occurs in ids[r]: y = x * theta if x < 0 else x / theta (IEEE division); theta = 1: the identity;
+      n-gram   n > 0 and cur >= n: for every i in [0, cur - n] with ids[r, i : i+n-1] == ids[r, cur-n+1 : cur], column ids[r, i+n-1] is banned
+               (n = 1: every token seen).
+    A banned column wins over a penalised one (the caller removes it); history tokens outside [0, V) are ignored by both rules."""
+    check_edit_args(repetition_penalty, no_repeat_ngram_size)
+    n = int(no_repeat_ngram_size)
+    x = x if x.dtype == torch.float64 else x.float()
+    R, V = x.shape
+    cur = ids.shape[1]
+    inside = (ids >= 0) & (ids < V)
+    row = torch.arange(R, device=x.device)[:, None].expand(R, cur)
+    seen = torch.zeros(R, V, dtype=torch.bool, device=x.device)
+    seen[row[inside], ids[inside]] = True
+    theta = torch.tensor(float(repetition_penalty), dtype=x.dtype, device=x.device)      # a tensor: tensor / tensor is a true division everywhere
+    y = torch.where(seen, torch.where(x < 0, x * theta, x / theta), x)
+    banned = torch.zeros(R, V, dtype=torch.bool, device=x.device)
+    if n > 0 and cur >= n:
+        win = ids.unfold(1, n, 1)                                                         # [R, cur - n + 1, n]
+        match = (win[:, :, :n - 1] == ids[:, cur - n + 1:][:, None, :]).all(dim=-1)       # n = 1: no prefix to compare, every window matches
+        tok = win[:, :, n - 1]
+        hit = match & (tok >= 0) & (tok < V)
+        banned[row[:, :tok.shape[1]][hit], tok[hit]] = True
+    return y, banned
 
 
 def stable_topk(cand, k):
@@ -53,14 +105,18 @@ def stable_topk(cand, k):
 
 @torch.no_grad()
 def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
-                            length_penalty=1.0, reorder_fn=None, topk_fn=None):
+                            length_penalty=1.0, reorder_fn=None, topk_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """step_fn(ids [B*nb, T]) -> next-token logits [B*nb, V] (any float dtype) for the LAST position of every row.
     reorder_fn(rows int64 [B*nb]) is called after each step with the source row of every continuing beam (cache re-ordering).
     topk_fn(cand [B, nb*V], k) -> (values, indices), best first; None = `cand.topk(k, dim=1)`, whose order among equal candidates is
     torch's; `stable_topk` is the library's rule.
     Returns a list of B 1-D LongTensors (prompt + generated tokens, EOS included when the hypothesis ended with one).
     All tensor ops, on the device of input_ids -- but not free of host round trips there: every boolean-mask index below is a
-    `nonzero`, which waits for the device."""
+    `nonzero`, which waits for the device.
+    repetition_penalty / no_repeat_ngram_size: `decode_edits` on the log-probabilities (fp32) with ids[:, :cur] as history, before the beam
+    score is added, as transformers applies its processors: a penalised score is theta * logp, a banned column is no candidate, and the
+    beam scores accumulate the processed values."""
+    edit = _edits_on(repetition_penalty, no_repeat_ngram_size)
     B, T0 = input_ids.shape
     dev = input_ids.device
     nb = num_beams
@@ -94,6 +150,9 @@ def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_
         logits = step_fn(ids[:, :cur])
         logp = torch.log_softmax(logits.float(), dim=-1)
         V = logp.shape[-1]
+        if edit:
+            logp, banned = decode_edits(ids[:, :cur], logp, repetition_penalty, no_repeat_ngram_size)
+            logp[banned] = -float('inf')
         if cur < min_length:
             logp[:, eos_token_id] = -float('inf')
         cand = (beam_scores.view(-1, 1) + logp).view(B, nb * V)
@@ -145,13 +204,16 @@ def beam_search_from_logits(step_fn, input_ids, num_beams=3, max_length=20, min_
 
 @torch.no_grad()
 def beam_search_device(step_fn, input_ids, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
-                       length_penalty=1.0, reorder_fn=None, rows_rep=1):
+                       length_penalty=1.0, reorder_fn=None, rows_rep=1, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """beam_search_from_logits with the beam step in the library (ops.beam_topk, ops.beam_advance) and the search state in device
     buffers allocated once: same arguments, same return value, ties by the library's rule.
     step_fn(ids [B*nb, T]) -> bf16 logits on the GPU, [B*nb, V], or [B, V] when one row stands for all beams of its item (the first
     step after a per-image prefill).  reorder_fn(rows int32 [rows_rep * B*nb]) gets, for l < rows_rep, l * B*nb + the source row of
-    every continuing beam AMONG THE ROWS step_fn RETURNED (rows_rep > 1: the gather index of a stack of caches)."""
+    every continuing beam AMONG THE ROWS step_fn RETURNED (rows_rep > 1: the gather index of a stack of caches).
+    With repetition_penalty != 1 or no_repeat_ngram_size > 0 the step is ph_beam_topk_edit on the token rows of the search state (at most
+    EDIT_MAX_CUR tokens of history: max_length <= EDIT_MAX_CUR + 1); with both off it is ph_beam_topk, launch for launch what it was."""
     from .. import ops
+    edit = _edits_on(repetition_penalty, no_repeat_ngram_size)
     B, T0 = input_ids.shape
     dev = input_ids.device
     nb, Tmax = num_beams, max_length
@@ -176,7 +238,8 @@ def beam_search_device(step_fn, input_ids, num_beams=3, max_length=20, min_lengt
         if ws is None:
             ws = ops.beam_topk_workspace(B, nb, logits.shape[1], dev)
         nb_in = logits.shape[0] // B
-        ops.beam_topk(logits, beam_scores if nb_in == nb else first_scores, B, nb, eos_token_id, cur < min_length, workspace=ws, out=top)
+        ops.beam_topk(logits, beam_scores if nb_in == nb else first_scores, B, nb, eos_token_id, cur < min_length, workspace=ws, out=top,
+                      edits=(ids[which], cur, repetition_penalty, no_repeat_ngram_size) if edit else None)
         ops.beam_advance(top, ids[which], ids[which ^ 1], beam_scores, hyp_score, hyp_tok, hyp_len, n_hyp, done, rows, nb_in, cur,
                          eos_token_id, pad_token_id, float(cur) ** length_penalty)
         which ^= 1
@@ -206,29 +269,35 @@ def beam_search_device(step_fn, input_ids, num_beams=3, max_length=20, min_lengt
     return [out_tok[b, :int(out_len[b])].to(dev) for b in range(B)]
 
 
-def _device_beams_ok(device_beams, dev, nb):
+def _device_beams_ok(device_beams, dev, nb, edit=False, max_length=0):
     if device_beams is False:
         return False
-    ok = dev.type == 'cuda' and 1 <= nb <= 8
+    ok = dev.type == 'cuda' and 1 <= nb <= 8 and not (edit and max_length - 1 > EDIT_MAX_CUR)
     if device_beams and not ok:
-        raise ValueError('device_beams=True needs logits on the GPU and 1 <= num_beams <= 8')
+        raise ValueError(f'device_beams=True needs logits on the GPU, 1 <= num_beams <= 8 and, with repetition_penalty / no_repeat_ngram_size, '
+                         f'max_length <= {EDIT_MAX_CUR + 1}')
     return ok
 
 
 @torch.no_grad()
 def beam_search(decoder, input_ids, attention_mask, enc, num_beams=3, max_length=20, min_length=8, eos_token_id=2, pad_token_id=1,
-                length_penalty=1.0, use_cache=True, device_beams=None, share_image=True):
+                length_penalty=1.0, use_cache=True, device_beams=None, share_image=True, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """decoder: prismer_amd RobertaForCausalLMModified (eval mode); enc: [B, S, Hv] encoder states (one row per image).
     use_cache=False re-runs the full prefix every step like the reference (kept for the equivalence test).
     device_beams: None = the device beam step (beam_search_device) when the logits are bf16 on the GPU and num_beams <= 8, else the
     tensor form; False forces the tensor form (beam_search_from_logits).  Cached and recomputing decoding take the same beam step.
+    repetition_penalty / no_repeat_ngram_size: see `decode_edits`; the history is the whole row, prompt and pads included.  With them on,
+    a max_length beyond EDIT_MAX_CUR + 1 takes the tensor form.
     share_image: the beams of an image share its cross-attention K/V and the prompt runs once per image; False tiles every image
     num_beams times before anything runs (the earlier layout, kept for A/B measurements)."""
     B, T0 = input_ids.shape
     nb = num_beams
-    on_device = _device_beams_ok(device_beams, input_ids.device, nb)
+    edit = _edits_on(repetition_penalty, no_repeat_ngram_size)
+    on_device = _device_beams_ok(device_beams, input_ids.device, nb, edit, max_length)
     kw = dict(num_beams=nb, max_length=max_length, min_length=min_length, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
               length_penalty=length_penalty)
+    if edit:
+        kw.update(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
     search = beam_search_device if on_device else beam_search_from_logits
     att_b = torch.cat([attention_mask.repeat_interleave(nb, dim=0), attention_mask.new_ones(B * nb, max(max_length - T0, 0))], dim=1)
 
@@ -304,16 +373,18 @@ def check_sampling_args(temperature=1.0, top_k=50, top_p=1.0, num_return_sequenc
         raise ValueError(f'num_return_sequences must be an integer >= 1, got {num_return_sequences}')
 
 
-def sample_filter(x, temperature=1.0, top_k=50, top_p=1.0, banned_col=None):
+def sample_filter(x, temperature=1.0, top_k=50, top_p=1.0, banned_col=None, banned=None):
     """The kept set of every row of x (fp32 [R, V]: bf16 logits read as fp32) as (keep bool [R, V], z float64 [R, V] = x / temperature).
     Candidates are the finite columns (a NaN is never one; -inf is what transformers' own filters write for a removed token; +inf has
-    no distribution) but `banned_col`.  Top-k keeps z >= the k-th largest z, ties included.  Top-p works on classes of equal logit over
+    no distribution) but `banned_col` and the columns of the optional mask `banned` (bool [R, V]).  Top-k keeps z >= the k-th largest z, ties included.  Top-p works on classes of equal logit over
     what top-k kept: a class stays iff the mass of the strictly higher classes is < top_p, so the top class always stays and the kept set is
     a threshold set -- TopPLogitsWarper's rule but inside the boundary class, which transformers cuts by sort position."""
     x = x.float()
     cand = torch.isfinite(x)
     if banned_col is not None:
         cand[:, banned_col] = False
+    if banned is not None:
+        cand = cand & ~banned
     z = x.double() / float(temperature)
     ninf = torch.full_like(z, -float('inf'))
     keep = cand
@@ -359,7 +430,7 @@ def _trim_sampled(ids, T0, cur, eos_token_id):
 
 @torch.no_grad()
 def sample_from_logits(step_fn, input_ids, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50, top_p=1.0,
-                       eos_token_id=2, pad_token_id=1, seed=0, uniforms=None, reorder_fn=None):
+                       eos_token_id=2, pad_token_id=1, seed=0, uniforms=None, reorder_fn=None, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """Sampled decoding as tensor ops: the SPECIFICATION of ph_sample_step / sample_device (transformers' generate(do_sample=True):
     MinLengthLogitsProcessor -> TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial, bookkeeping of _sample).
     step_fn(ids [B*n, T]) -> next-token logits for the last position, [B*n, V], or [B, V] when one row stands for the n rows of its
@@ -368,8 +439,13 @@ def sample_from_logits(step_fn, input_ids, num_return_sequences=1, max_length=20
     `sample_filter` (EOS banned while cur < min_length), `sample_draw` with u = uniforms[r, cur] or `sample_uniforms`; a finished row
     emits pad, a row that draws EOS is finished, a row without candidates emits EOS and is finished (its log-probability stays).
     Returns (ids [B*n, L] padded with pad_token_id, L = the longest row, EOS included; seq_logprob fp32 [B*n] = the sum of
-    log_softmax(raw fp32 row)[token] over the drawn tokens: temperature 1, no filter, no ban)."""
+    log_softmax(raw fp32 row)[token] over the drawn tokens: temperature 1, no filter, no ban).
+    repetition_penalty / no_repeat_ngram_size: `decode_edits` on the row (bf16 read as fp32) with ids[r, :cur] as history; the result is
+    rounded back to bf16 (nearest even) -- again a row of bf16 logits, the one deviation from transformers: relative 2^-9 on penalised
+    logits -- and everything downstream runs on it with the banned columns joined to the non-candidates; the log-probability stays the RAW
+    row's."""
     check_sampling_args(temperature, top_k, top_p, num_return_sequences)
+    edit = _edits_on(repetition_penalty, no_repeat_ngram_size)
     B, T0 = input_ids.shape
     dev = input_ids.device
     n, Tmax = int(num_return_sequences), max_length
@@ -385,7 +461,11 @@ def sample_from_logits(step_fn, input_ids, num_return_sequences=1, max_length=20
         x = logits.bfloat16().float()
         if shared:
             x = x.repeat_interleave(n, dim=0)
-        keep, z = sample_filter(x, temperature, top_k, top_p, eos_token_id if cur < min_length else None)
+        xe, banned = x, None
+        if edit:
+            y, banned = decode_edits(ids[:, :cur], x, repetition_penalty, no_repeat_ngram_size)
+            xe = y.bfloat16().float()
+        keep, z = sample_filter(xe, temperature, top_k, top_p, eos_token_id if cur < min_length else None, banned=banned)
         u = (sample_uniforms(R, cur, seed) if uniforms is None else uniforms[:, cur].float().cpu()).to(dev)
         tok = sample_draw(keep, z, u)
         empty = tok < 0
@@ -402,13 +482,15 @@ def sample_from_logits(step_fn, input_ids, num_return_sequences=1, max_length=20
 
 @torch.no_grad()
 def sample_device(step_fn, input_ids, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50, top_p=1.0,
-                  eos_token_id=2, pad_token_id=1, seed=0, reorder_fn=None, rows_rep=1):
+                  eos_token_id=2, pad_token_id=1, seed=0, reorder_fn=None, rows_rep=1, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """sample_from_logits with the step in the library (ops.sample_step: one launch per position for all rows) on state allocated once:
     same arguments (no `uniforms`), same return value.  step_fn -> bf16 logits on the GPU; reorder_fn(rows int32 [rows_rep * B*n]) gets,
     once, after a step whose logits had one row per image, l * B*n + r // n for l < rows_rep.  The one host read is the "all rows
-    done?" check every fourth step."""
+    done?" check every fourth step.  With repetition_penalty != 1 or no_repeat_ngram_size > 0 the step is ph_sample_step_edit (max_length <=
+    EDIT_MAX_CUR + 1); with both off it is ph_sample_step."""
     from .. import ops
     check_sampling_args(temperature, top_k, top_p, num_return_sequences)
+    edits = (repetition_penalty, no_repeat_ngram_size) if _edits_on(repetition_penalty, no_repeat_ngram_size) else None
     B, T0 = input_ids.shape
     dev = input_ids.device
     n, Tmax = int(num_return_sequences), max_length
@@ -420,7 +502,7 @@ def sample_device(step_fn, input_ids, num_return_sequences=1, max_length=20, min
     cur = T_start = T0
     while cur < Tmax:
         logits = step_fn(ids[:, :cur])
-        ops.sample_step(logits, ids, done, logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, cur < min_length, seed)
+        ops.sample_step(logits, ids, done, logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, cur < min_length, seed, edits=edits)
         if logits.shape[0] != R and reorder_fn is not None:
             i32 = torch.int32
             rows = torch.arange(R, device=dev, dtype=i32) // n
@@ -431,18 +513,20 @@ def sample_device(step_fn, input_ids, num_return_sequences=1, max_length=20, min
     return _trim_sampled(ids, T0, cur, eos_token_id), logprob
 
 
-def _device_sample_ok(device_sample, dev, V):
+def _device_sample_ok(device_sample, dev, V, edit=False, max_length=0):
     if device_sample is False:
         return False
-    ok = dev.type == 'cuda' and 8 <= V <= SAMPLE_MAX_V
+    ok = dev.type == 'cuda' and 8 <= V <= SAMPLE_MAX_V and not (edit and max_length - 1 > EDIT_MAX_CUR)
     if device_sample and not ok:
-        raise ValueError(f'device_sample=True needs logits on the GPU and 8 <= vocabulary <= {SAMPLE_MAX_V}')
+        raise ValueError(f'device_sample=True needs logits on the GPU, 8 <= vocabulary <= {SAMPLE_MAX_V} and, with repetition_penalty / '
+                         f'no_repeat_ngram_size, max_length <= {EDIT_MAX_CUR + 1}')
     return ok
 
 
 @torch.no_grad()
 def sample(decoder, input_ids, attention_mask, enc, num_return_sequences=1, max_length=20, min_length=0, temperature=1.0, top_k=50,
-           top_p=1.0, eos_token_id=2, pad_token_id=1, seed=0, use_cache=True, device_sample=None, share_image=True):
+           top_p=1.0, eos_token_id=2, pad_token_id=1, seed=0, use_cache=True, device_sample=None, share_image=True, repetition_penalty=1.0,
+           no_repeat_ngram_size=0):
     """Sampled decoding with the decoder, the counterpart of `beam_search`: n = num_return_sequences rows per image, row image * n + j.
     Returns (ids [B*n, L], seq_logprob [B*n]) as `sample_from_logits` does.
     device_sample: None = the device step (sample_device) when the logits are bf16 on the GPU and the vocabulary fits ph_sample_step,
@@ -450,13 +534,17 @@ def sample(decoder, input_ids, attention_mask, enc, num_return_sequences=1, max_
     share_image: the n rows of an image share its cross-attention K/V (decode_begin(beams=n)), the prompt runs once per image and one
     decode_reorder (source row r // n) hands the prompt's cache rows out; nothing is re-ordered afterwards.  n = 1 needs neither.  The
     grouped decode step is used with up to SAMPLE_MAX_GROUP rows per image (what the beam search exercises); a larger n, or
-    share_image=False, tiles every image n times before anything runs."""
+    share_image=False, tiles every image n times before anything runs.
+    repetition_penalty / no_repeat_ngram_size: see `sample_from_logits`; with them on, a max_length beyond EDIT_MAX_CUR + 1 takes the tensor form."""
     check_sampling_args(temperature, top_k, top_p, num_return_sequences)
     B, T0 = input_ids.shape
     n = int(num_return_sequences)
-    on_device = _device_sample_ok(device_sample, input_ids.device, decoder.config.vocab_size)
+    edit = _edits_on(repetition_penalty, no_repeat_ngram_size)
+    on_device = _device_sample_ok(device_sample, input_ids.device, decoder.config.vocab_size, edit, max_length)
     kw = dict(num_return_sequences=n, max_length=max_length, min_length=min_length, temperature=temperature, top_k=top_k, top_p=top_p,
               eos_token_id=eos_token_id, pad_token_id=pad_token_id, seed=seed)
+    if edit:
+        kw.update(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
     search = sample_device if on_device else sample_from_logits
     att_b = torch.cat([attention_mask.repeat_interleave(n, dim=0), attention_mask.new_ones(B * n, max(max_length - T0, 0))], dim=1)
     if not use_cache:

@@ -22,9 +22,12 @@ class PrismerCaption(Prismer):
         t = self._tokenize(text, return_tensors='pt', **kw).to(device)
         return t.input_ids, t.attention_mask
 
-    def forward(self, experts, caption=None, answer=None, train=True, prefix='', inference='generate', k_test=32, return_scores=False, sample=None):
+    def forward(self, experts, caption=None, answer=None, train=True, prefix='', inference='generate', k_test=32, return_scores=False, sample=None,
+                generate_args=None):
         """sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
-        num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences captions, image-major."""
+        num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences captions, image-major.
+        generate_args: None, or a dict of further arguments of `text_decoder.generate` for the beam search (repetition_penalty,
+        no_repeat_ngram_size); the `sample` dict carries them for sampled decoding."""
         device = experts['rgb'].device
         pad = self.text_decoder.config.pad_token_id
         if train:
@@ -50,7 +53,7 @@ class PrismerCaption(Prismer):
                 ids, att = ids[:, :-1], att[:, :-1]                                        # drop </s>
                 if sample is None:
                     outputs = self.text_decoder.generate(input_ids=ids, encoder_hidden_states=experts_train, attention_mask=att, num_beams=3,
-                                                         max_length=20, min_length=8)       # prismer_caption.py:45-50
+                                                         max_length=20, min_length=8, **(generate_args or {}))       # prismer_caption.py:45-50
                 else:
                     outputs = self.text_decoder.generate(input_ids=ids, encoder_hidden_states=experts_train, attention_mask=att, do_sample=True,
                                                          max_length=20, min_length=8, **sample)

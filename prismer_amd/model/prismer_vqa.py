@@ -14,9 +14,12 @@ class PrismerVQA(Prismer):
         t = self._tokenize(text, return_tensors='pt', **kw).to(device)
         return t.input_ids, t.attention_mask
 
-    def forward(self, experts, question, answer=None, weights=None, train=True, inference='rank', k_test=128, return_scores=False, sample=None):
+    def forward(self, experts, question, answer=None, weights=None, train=True, inference='rank', k_test=128, return_scores=False, sample=None,
+                generate_args=None):
         """sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
-        num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences answers, image-major."""
+        num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences answers, image-major.
+        generate_args: None, or a dict of further arguments of `text_decoder.generate` for the beam search (repetition_penalty,
+        no_repeat_ngram_size); the `sample` dict carries them for sampled decoding."""
         device = experts['rgb'].device
         pad = self.text_decoder.config.pad_token_id
         if isinstance(question, (list, tuple)) and question and isinstance(question[0], str):
@@ -43,7 +46,7 @@ class PrismerVQA(Prismer):
                 if sample is None:
                     out = self.text_decoder.generate(input_ids=q_ids, encoder_hidden_states=enc, attention_mask=q_att,
                                                      max_length=q_ids.shape[1] + 10, min_length=q_ids.shape[1] + 2, num_beams=3,
-                                                     length_penalty=-1)                     # prismer_vqa.py:52-58
+                                                     length_penalty=-1, **(generate_args or {}))         # prismer_vqa.py:52-58
                 else:
                     out = self.text_decoder.generate(input_ids=q_ids, encoder_hidden_states=enc, attention_mask=q_att, do_sample=True,
                                                      max_length=q_ids.shape[1] + 10, min_length=q_ids.shape[1] + 2, **sample)

@@ -236,13 +236,17 @@ class RobertaForCausalLMModified(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, encoder_hidden_states=None, attention_mask=None, num_beams=1, max_length=20, min_length=0,
                  length_penalty=1.0, do_sample=False, top_k=50, top_p=1.0, temperature=1.0, num_return_sequences=1, seed=None,
-                 return_logprobs=False, **unused):
+                 return_logprobs=False, repetition_penalty=1.0, no_repeat_ngram_size=0, **unused):
         """transformers' `generate` as the heads call it (model/prismer_caption.py:45-50, model/prismer_vqa.py:52-58): beam search,
         returns a [B, L] LongTensor padded with pad_token_id.  KV-cached on the HIP path (the reference re-runs the prefix).
         do_sample=True: sampled decoding (model/generate.py::sample) with transformers' temperature / top_k / top_p, returns
         [B * num_return_sequences, L], image-major; with return_logprobs also each row's model log-probability (fp32 [B * n]).  seed=None
-        takes torch.initial_seed() plus a per-module call counter: two calls differ, torch.manual_seed makes a run repeatable."""
-        from ..model.generate import beam_search, check_sampling_args, sample
+        takes torch.initial_seed() plus a per-module call counter: two calls differ, torch.manual_seed makes a run repeatable.
+        repetition_penalty / no_repeat_ngram_size: transformers' two processors in both modes (model/generate.py::decode_edits); the history
+        of a row is all of it, prompt and pad tokens included."""
+        from ..model.generate import beam_search, check_edit_args, check_sampling_args, sample
+        check_edit_args(repetition_penalty, no_repeat_ngram_size)
+        edits = dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
         if attention_mask is None:
             attention_mask = input_ids.new_ones(input_ids.shape)
         c = self.config
@@ -255,13 +259,13 @@ class RobertaForCausalLMModified(nn.Module):
                 seed = (torch.initial_seed() + self._sample_calls) & 0xFFFFFFFFFFFFFFFF
             ids, logprob = sample(self, input_ids, attention_mask, encoder_hidden_states, num_return_sequences=num_return_sequences,
                                   max_length=max_length, min_length=min_length, temperature=temperature, top_k=top_k, top_p=top_p,
-                                  eos_token_id=getattr(c, 'eos_token_id', 2), pad_token_id=c.pad_token_id, seed=seed)
+                                  eos_token_id=getattr(c, 'eos_token_id', 2), pad_token_id=c.pad_token_id, seed=seed, **edits)
             return (ids, logprob) if return_logprobs else ids
         if num_return_sequences != 1:
             raise ValueError('generate: num_return_sequences > 1 needs do_sample=True')
         outs = beam_search(self, input_ids, attention_mask, encoder_hidden_states, num_beams=num_beams, max_length=max_length,
                            min_length=min_length, eos_token_id=getattr(c, 'eos_token_id', 2), pad_token_id=c.pad_token_id,
-                           length_penalty=length_penalty)
+                           length_penalty=length_penalty, **edits)
         L = max(int(o.numel()) for o in outs)
         res = input_ids.new_full((len(outs), L), c.pad_token_id)
         for i, o in enumerate(outs):

@@ -811,10 +811,12 @@ def beam_topk_workspace(B, nb, V, device):
     return torch.empty(n // 4, dtype=F32, device=device)
 
 
-def beam_topk(logits, beam_scores, B, nb, eos_token_id, ban_eos, workspace=None, out=None):
+def beam_topk(logits, beam_scores, B, nb, eos_token_id, ban_eos, workspace=None, out=None, edits=None):
     """The best 2*nb candidates of every item, best first: (top_score fp32, top_beam int32, top_tok int32), each [B, 2*nb], of
     beam_scores[row] + log_softmax(logits[row]) over bf16 logit rows [B*nb or B, V] (a strided view is fine: row stride a multiple of 8
-    elements, rows 16-B aligned).  B rows = one row per item (all its beams share it, beam 0 is reported).  Ties: flat index ascending."""
+    elements, rows 16-B aligned).  B rows = one row per item (all its beams share it, beam 0 is reported).  Ties: flat index ascending.
+    edits: None, or (ids int64 [B*nb, >= cur], cur, repetition_penalty, no_repeat_ngram_size): ph_beam_topk_edit, the two processors on the
+    log-probabilities with ids[:, :cur] as every beam's history."""
     assert logits.dim() == 2 and logits.dtype == BF16 and logits.stride(1) == 1 and beam_scores.dtype == F32 and beam_scores.is_contiguous()
     R, V = logits.shape
     assert R in (B, B * nb) and beam_scores.numel() == R, 'beam_topk: one logit row and one score per beam, or one per item'
@@ -825,7 +827,13 @@ def beam_topk(logits, beam_scores, B, nb, eos_token_id, ban_eos, workspace=None,
                torch.empty((B, 2 * nb), dtype=torch.int32, device=logits.device))
     a = _lib.BeamTopkArgs(logits.data_ptr(), logits.stride(0), V, B, nb, R // B, beam_scores.data_ptr(), int(eos_token_id), int(bool(ban_eos)),
                           workspace.data_ptr(), workspace.numel() * workspace.element_size(), out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
-    check(lib.ph_beam_topk(C.byref(a), _stream()), 'ph_beam_topk')
+    if edits is None:
+        check(lib.ph_beam_topk(C.byref(a), _stream()), 'ph_beam_topk')
+        return out
+    ids, cur, penalty, ngram = edits
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.shape[0] == B * nb and ids.stride(1) == 1 and ids.device == logits.device, \
+        'beam_topk: ids int64 [B*nb, T] on the device of the logits'
+    check(lib.ph_beam_topk_edit(C.byref(a), ids.data_ptr(), ids.stride(0), int(cur), float(penalty), int(ngram), _stream()), 'ph_beam_topk_edit')
     return out
 
 
@@ -847,11 +855,12 @@ def beam_advance(top, ids_in, ids_out, beam_scores, hyp_score, hyp_tok, hyp_len,
     check(lib.ph_beam_advance(C.byref(a), _stream()), 'ph_beam_advance')
 
 
-def sample_step(logits, ids, done, seq_logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, ban_eos, seed, diag=None):
+def sample_step(logits, ids, done, seq_logprob, cur, temperature, top_k, top_p, eos_token_id, pad_token_id, ban_eos, seed, diag=None, edits=None):
     """One sampled decoding step for every row (see ph_sample_step): over bf16 logit rows [R, V], or [R / n, V] when n consecutive rows share
     one (a strided view is fine: row stride a multiple of 8 elements, rows 16-B aligned), it writes ids[:, cur] (int64 [R, Tmax]), done (int32 [R]) and seq_logprob (fp32 [R]) in place.
     The draw of row r is a function of (seed, r, cur) alone.  diag: None or (u fp32, thr fp32, kept_count int32, kept_mass fp32), [R] each,
-    any of them None."""
+    any of them None.  edits: None, or (repetition_penalty, no_repeat_ngram_size): ph_sample_step_edit, the two processors on the row first,
+    with ids[r, :cur] as row r's history."""
     assert logits.dim() == 2 and logits.dtype == BF16 and logits.stride(1) == 1
     Rl, V = logits.shape
     R = ids.shape[0]
@@ -864,7 +873,10 @@ def sample_step(logits, ids, done, seq_logprob, cur, temperature, top_k, top_p, 
     a = _lib.SampleStepArgs(logits.data_ptr(), logits.stride(0), V, R, R // Rl, ids.shape[1], int(cur), ids.data_ptr(), done.data_ptr(), seq_logprob.data_ptr(),
                             float(temperature), float(top_p), int(top_k), int(eos_token_id), int(pad_token_id), int(bool(ban_eos)),
                             int(seed) & 0xFFFFFFFFFFFFFFFF, *(None if t is None else t.data_ptr() for t in d))
-    check(lib.ph_sample_step(C.byref(a), _stream()), 'ph_sample_step')
+    if edits is None:
+        check(lib.ph_sample_step(C.byref(a), _stream()), 'ph_sample_step')
+    else:
+        check(lib.ph_sample_step_edit(C.byref(a), float(edits[0]), int(edits[1]), _stream()), 'ph_sample_step_edit')
 
 
 def ce_bwd(logits, labels, B, T, V, eps, row_lse, dloss):

@@ -11,7 +11,11 @@ Prismer-BASE decoder with synthetic weights, random encoder states of the leg's 
     python tools/generate_probe.py [--reps N] [--out FILE]        all legs
     python tools/generate_probe.py --profile [--arm new|parent]   one warm-up + one call of the first leg (for rocprofv3 --kernel-trace --stats)
     python tools/generate_probe.py --sample [--reps N] [--out FILE]   sampled decoding (top_p 0.9, n = 1 and 5 per image, caption 480^2 B=32): the
-        tensor form (sample(device_sample=False)) against the device step (ph_sample_step), medians of alternating calls"""
+        tensor form (sample(device_sample=False)) against the device step (ph_sample_step), medians of alternating calls
+    python tools/generate_probe.py --edits [--reps N] [--out FILE]    repetition_penalty / no_repeat_ngram_size on the device step: the beam and the
+        sampled (n = 5) leg of caption 480^2 B=32 with (theta, n) = (1, 0) -- the plain entry points -- against (1.2, 3) -- ph_beam_topk_edit /
+        ph_sample_step_edit --, alternating in one process; run it on the parent commit too (there the options are swallowed: both arms are
+        "off") to compare the off arm across commits"""
 import argparse
 import ctypes as C
 import os
@@ -119,9 +123,53 @@ def sample_arm(dec, d, reps, say):
         say(f'{n:3d} tensor / device = {median(times["tensor"]) / median(times["device"]):.2f}x (medians)')
 
 
+def edits_arm(dec, d, reps, say):
+    """ms per call with the two options off (1, 0) and on (1.2, 3): beam search (3 beams) and sampled decoding (n = 5), device step"""
+    leg = LEGS[0]
+    name, res, B, Tq, ragged, Tmax, Tmin, lp = leg
+    enc, q, qa, S = inputs(d, B, Tq, ragged, res, 0)
+    arms = [('off', dict(repetition_penalty=1.0, no_repeat_ngram_size=0)), ('on', dict(repetition_penalty=1.2, no_repeat_ngram_size=3))]
+    import inspect
+    if 'repetition_penalty' not in inspect.signature(beam_search).parameters:     # a commit before the options: both arms are the plain step
+        arms = [(a, {}) for a, _ in arms]
+        say('this commit has no repetition_penalty / no_repeat_ngram_size: both arms run the plain entry points')
+    say(f'{name}: off = (repetition_penalty 1, no_repeat_ngram_size 0): ph_beam_topk / ph_sample_step;  on = (1.2, 3): ph_beam_topk_edit / ph_sample_step_edit')
+    say(f'{"leg":14s} {"arm":4s} {"ms/call median":>15s} {"half medians":>19s} {"spread":>8s} {"steps":>6s}')
+
+    def beam(kw, seed):
+        ms, _, out = call(dec, d, enc, q, qa, leg, kw)
+        return ms, max(len(o) for o in out) - Tq
+
+    def sampled(kw, seed):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            ids, _ = sample(dec, q, qa, enc, num_return_sequences=5, max_length=Tmax, min_length=Tmin, top_k=0, top_p=0.9,
+                            eos_token_id=d.eos_token_id, pad_token_id=d.pad_token_id, seed=seed, **kw)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, ids.shape[1] - Tq
+    for lname, run in (('beam 3', beam), ('sampled n=5', sampled)):
+        for _, kw in arms:
+            run(kw, 0)                                                             # warm-up of both
+        times, steps = {a: [] for a, _ in arms}, {}
+        for i in range(reps):                                                      # alternating, the same seed for both arms of a round
+            for a, kw in arms:
+                ms, steps[a] = run(kw, 1 + i)
+                times[a].append(ms)
+        spread = 0.0
+        for a, _ in arms:
+            t = times[a]
+            h0, h1 = median(t[:len(t) // 2]), median(t[len(t) // 2:])
+            spread = max(spread, abs(h0 - h1))
+            say(f'{lname:14s} {a:4s} {median(t):15.2f} {h0:9.2f} {h1:9.2f} {abs(h0 - h1):8.2f} {steps[a]:6d}')
+        diff = median(times['on']) - median(times['off'])
+        say(f'{lname:14s} on - off = {diff:+.2f} ms per call = {diff / max(steps["on"], 1) * 1e3:+.1f} us per decode step (medians; spread of the half medians {spread:.2f} ms)')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sample', action='store_true')
+    ap.add_argument('--edits', action='store_true')
     ap.add_argument('--reps', type=int, default=12)
     ap.add_argument('--out', default=None)
     ap.add_argument('--profile', action='store_true')
@@ -147,9 +195,9 @@ def main():
         return
     reps = max(args.reps, 10)
     props = torch.cuda.get_device_properties(0)
-    if args.sample:
+    if args.sample or args.edits:
         say(f'device: {props.name}, {props.total_memory / 2**30:.0f} GiB; Prismer-BASE decoder (synthetic weights), random encoder states')
-        sample_arm(dec, d, reps, say)
+        (edits_arm if args.edits else sample_arm)(dec, d, reps, say)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, 'w') as f:
