@@ -557,6 +557,17 @@ int ph_clip_finalize(const double* partials, int n_partials, double pre_scale, f
 int ph_adamw_ctl(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
                  float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
                  hipStream_t stream);
+/* ph_adamw_keep (ctl == NULL) / ph_adamw_ctl with an exponential moving average of the weights updated in the same pass -- the weights that
+ * timm.utils.ModelEma or torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn keep beside the model, which the reference loop
+ * (train_caption.py:121-136) would update with one lerp_ per parameter after optimizer.step().  `ema`: fp32, n elements, 16-byte aligned;
+ * `ema_w`: ONE fp32 in device memory, w = 1 - decay of this update (read from device memory like hyper: hipGraph replays see new values).
+ * Per element, with p' the new master value:  e' = e + w * (p' - e)  in fp32 (an fma contraction is allowed); the n & 3 tail elements too.
+ * p, g, m, v and the shadow come out bit for bit as from ph_adamw_keep / ph_adamw_ctl; with ctl->apply == 0 `ema` keeps its bits like
+ * p, m, v and the shadow, and the gradient clean-up is ph_adamw_ctl's.  HBM traffic: 38 B per parameter (30 + one fp32 stream read and
+ * written; a separate pass would move 12). */
+int ph_adamw_ema(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
+                 float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
+                 float* ema, const float* ema_w, hipStream_t stream);
 int ph_cast_f32_to_bf16(const float* x, void* y, int64_t n, hipStream_t stream);
 int ph_cast_bf16_to_f32(const void* x, float* y, int64_t n, hipStream_t stream);
 /* y = bf16(x * scale): the gradient pack of the bf16 exchange payload, pre-scaled by 1/world BEFORE the rounding (round 3) */
@@ -630,6 +641,10 @@ int ph_add_i64(int64_t* x, int n, int64_t value, hipStream_t stream);
  * so that a captured segment contains no memset / memcpy node (revision 103) */
 int ph_fill_zero(void* p, int64_t bytes, hipStream_t stream);
 int ph_copy_bytes(void* dst, const void* src, int64_t bytes, hipStream_t stream);
+/* a[0..n) <-> b[0..n) (fp32, both 16-byte aligned): an exact exchange through registers, 16-byte vectors plus a tail, no temporary -- the
+ * master weights against their moving average around an evaluation (Trainer.ema_weights).  Overlapping or misaligned ranges are
+ * PH_ERR_BAD_ARG before any launch. */
+int ph_swap_f32(float* a, float* b, int64_t n, hipStream_t stream);
 /* out[0] = scale * sum_i x[i] * (weights ? weights[i] : 1): the batch loss -- caption loss.mean() (prismer_caption.py:33) with scale = 1/B,
  * VQA (weights * loss).mean() (prismer_vqa.py:40-41) */
 int ph_weighted_sum_f32(const float* x, const float* weights, int n, float scale, float* out, hipStream_t stream);

@@ -230,6 +230,8 @@ _SIGS = {
                               c_float, c_float, c_int, c_void_p, c_void_p]),
     'ph_adamw_ctl': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,
                              c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    'ph_adamw_ema': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_float, c_float, c_float,
+                             c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ph_grad_sqnorm': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     'ph_clip_finalize': (c_int, [c_void_p, c_int, C.c_double, c_float, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p]),
     'ph_cast_f32_to_bf16': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
@@ -261,6 +263,7 @@ _SIGS = {
     'ph_add_i64': (c_int, [c_void_p, c_int, c_i64, c_void_p]),
     'ph_fill_zero': (c_int, [c_void_p, c_i64, c_void_p]),
     'ph_copy_bytes': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
+    'ph_swap_f32': (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
     'ph_weighted_sum_f32': (c_int, [c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p]),
     'ph_prof_enable': (c_int, [c_int]),
     'ph_prof_collect': (c_int, [c_void_p]),

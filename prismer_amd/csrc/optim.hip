@@ -12,11 +12,15 @@ namespace {
 // HBM-bound: 16 B read + 14 B written per parameter.
 // CTL (ph_adamw_ctl): the control block ph_clip_finalize wrote in front of this launch scales the gradients once more (clip coefficient) or
 // turns the launch into its gradient clean-up alone (skipped update).  CTL = false is the kernel as it always was: no extra argument is read.
-template <bool CTL>
+// EMA (ph_adamw_ema): the new master value is still in a register when it is stored, so the exponential moving average of the weights
+// e += w (p' - e), w = ema_w[0] read from device memory like hyper, rides the same walk: one more fp32 stream read and written (8 B/parameter on
+// top of 30; a pass of its own would move 12).  A skipped update returns before it.  EMA = false reads neither argument.
+template <bool CTL, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16* __restrict__ pb, int64_t n, const float* __restrict__ hyper,
                                                     float b1, float b2, float eps, float wd, float gscale, int zero_g, int mode,
-                                                    const uint32_t* __restrict__ keep, const ph_clip_ctl* __restrict__ ctl) {
+                                                    const uint32_t* __restrict__ keep, const ph_clip_ctl* __restrict__ ctl,
+                                                    float* __restrict__ ema, const float* __restrict__ ema_w) {
   if (CTL) {
     gscale *= ctl->coef;
     if (!ctl->apply) {
@@ -34,6 +38,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   }
   const float lr = hyper[0], bc1 = hyper[1], bc2 = hyper[2];
   const float step = lr / bc1, rbc2 = rsqrtf(bc2), decay = 1.f - lr * wd;
+  const float ew = EMA ? ema_w[0] : 0.f;
   int64_t n4 = n >> 2;
 #ifndef PH_ADAMW_NT
 #define PH_ADAMW_NT 0
@@ -65,6 +70,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       ob[e] = f2bf(pp);
     }
   };
+  auto average = [&](f32x4& te, const f32x4& tp) {      // (after update: tp holds the new masters)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) te[e] = te[e] + ew * (tp[e] - te[e]);
+  };
   if (mode == 1) {
     // Every block owns ONE contiguous chunk of each of the nine streams (round 5; rounds 1-4 walked the buffers with a grid stride: at any
     // moment the 2048 blocks then touched 2048 separate 4-KB pieces of every stream) and keeps two 16-B vectors per stream and thread in
@@ -74,11 +83,12 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     const int64_t per = ((n4 + gridDim.x - 1) / gridDim.x + 255) / 256 * 256;          // whole 1024-gradient chunks (keep bitmap granularity)
     const int64_t lo = (int64_t)blockIdx.x * per, hi = lo + per < n4 ? lo + per : n4;
     for (int64_t i0 = lo + threadIdx.x; i0 < hi; i0 += (int64_t)U * 256) {
-      f32x4 tp[U], tg[U], tm[U], tv[U];
+      f32x4 tp[U], tg[U], tm[U], tv[U], te[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t i = i0 + u * 256 < hi ? i0 + u * 256 : i0;
         tp[u] = LD4(p, i); tg[u] = LD4(g, i); tm[u] = LD4(m, i); tv[u] = LD4(v, i);
+        if (EMA) te[u] = LD4(ema, i);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -87,6 +97,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
           bf16x4 ob;
           update(tp[u], tg[u], tm[u], tv[u], ob);
           ST4(p, i, tp[u]); ST4(m, i, tm[u]); ST4(v, i, tv[u]);
+          if (EMA) { average(te[u], tp[u]); ST4(ema, i, te[u]); }
           if (pb) reinterpret_cast<bf16x4*>(pb)[i] = ob;
           if (zero_vec(i)) ST4(g, i, (f32x4{0.f, 0.f, 0.f, 0.f}));
         }
@@ -101,6 +112,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
       ST4(p, i, tp);
       ST4(m, i, tm);
       ST4(v, i, tv);
+      if (EMA) { f32x4 te = LD4(ema, i); average(te, tp); ST4(ema, i, te); }
       if (pb) reinterpret_cast<bf16x4*>(pb)[i] = ob;
       if (zero_vec(i)) ST4(g, i, (f32x4{0.f, 0.f, 0.f, 0.f}));      // optimizer.zero_grad() of the NEXT step
     }
@@ -113,6 +125,21 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     p[i] = pp; m[i] = mm; v[i] = vv;
     if (pb) pb[i] = f2bf(pp);
     if (zero_g) g[i] = 0.f;
+  }
+  if (EMA && (n & 3) && blockIdx.x == 0) {
+    // the average of the tail elements, by the SECOND wave of block 0 from the masters the first wave just stored.  Kept out of the block
+    // above on purpose: with the average's arithmetic in it the compiler pairs the AdamW multiplications into packed operations and drops the
+    // fma contraction of p * decay - step * ..., and the tail's p and v come out one ulp from ph_adamw_keep's (seen on the device).
+    // Bitwise equality with ph_adamw_keep / ph_adamw_ctl -- here and in the vector body, which shares the update lambda -- rests on the compiler
+    // contracting the same expressions the same way in every instantiation; nothing in the source pins it (explicit __fmaf_rn / __fmul_rn in the
+    // shared arithmetic would, at the price of touching the existing instantiations).  The guard is tests/test_ema_kernels_gpu.py: every size
+    // class, tail lengths 1 to 3, bit for bit against ph_adamw_keep and ph_adamw_ctl on the device.
+    __syncthreads();
+    if (threadIdx.x >= 64 && threadIdx.x - 64 < (n & 3)) {
+      const int64_t i = (n4 << 2) + threadIdx.x - 64;
+      const float ee = ema[i];
+      ema[i] = ee + ew * (p[i] - ee);
+    }
   }
 }
 
@@ -372,36 +399,51 @@ inline int grid_for(int64_t work_items) { return (int)std::min<int64_t>(ceil_div
 }  // namespace
 
 static int adamw_launch(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2, float eps,
-                        float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl, hipStream_t stream) {
+                        float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl, float* ema,
+                        const float* ema_w, hipStream_t stream) {
   PH_CHECK_ARG(p && g && m && v && hyper && n > 0, "ph_adamw: bad args");
   // (30 B/parameter is what an APPLIED launch moves; the host cannot know the device's decision, so a skipped ph_adamw_ctl launch -- at most
   // 4 B/parameter of zero stores, walked with a plain grid stride -- is booked the same: byte rates of the family are those of applied updates)
-  ProfScope prof__(PH_FAM_OPTIM, 0.0, 30.0 * (double)n, stream);
+  // (ph_adamw_ema: + 4 B read and 4 B written per parameter for the average)
+  ProfScope prof__(PH_FAM_OPTIM, 0.0, (ema ? 38.0 : 30.0) * (double)n, stream);
   PH_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && (((uintptr_t)p_bf16) & 7) == 0, "ph_adamw: misaligned");
   PH_CHECK_ARG((((uintptr_t)ctl) & 7) == 0, "ph_adamw_ctl: the control block must be 8-byte aligned");
+  PH_CHECK_ARG((((uintptr_t)ema) & 15) == 0 && (((uintptr_t)ema_w) & 3) == 0, "ph_adamw_ema: misaligned");
   constexpr int mode = 1;             // contiguous chunk per block, two vectors per stream in flight (0: the round-1 one-vector grid-stride loop)
   constexpr int blocks_cap = 2048;    // 8 blocks per CU
   int grid = grid_for(n / 4 + 1);
   if (blocks_cap > 0 && grid > blocks_cap) grid = blocks_cap;
-  if (ctl)
-    hipLaunchKernelGGL(adamw_kernel<true>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps,
-                       weight_decay, grad_scale, zero_grad, mode, keep_bitmap, ctl);
-  else
-    hipLaunchKernelGGL(adamw_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps,
-                       weight_decay, grad_scale, zero_grad, mode, keep_bitmap, (const ph_clip_ctl*)nullptr);
+#define PH_ADAMW_LAUNCH(CTL, EMA)                                                                                                          \
+  hipLaunchKernelGGL((adamw_kernel<CTL, EMA>), dim3(grid), dim3(256), 0, stream, p, g, m, v, (bf16*)p_bf16, n, hyper, beta1, beta2, eps, \
+                     weight_decay, grad_scale, zero_grad, mode, keep_bitmap, ctl, ema, ema_w)
+  if (ema) {
+    if (ctl) PH_ADAMW_LAUNCH(true, true);
+    else PH_ADAMW_LAUNCH(false, true);
+  } else {
+    if (ctl) PH_ADAMW_LAUNCH(true, false);
+    else PH_ADAMW_LAUNCH(false, false);
+  }
+#undef PH_ADAMW_LAUNCH
   PH_LAUNCH_CHECK("adamw_kernel");
   return PH_OK;
 }
 extern "C" int ph_adamw_keep(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
                              float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap,
                              hipStream_t stream) {
-  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, nullptr, stream);
+  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, nullptr, nullptr, nullptr, stream);
 }
 // the optimizer.step() of train_caption.py:133 behind clip_grad_norm_ / a scaler's skip: see include/prismer_hip.h
 extern "C" int ph_adamw_ctl(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
                             float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
                             hipStream_t stream) {
-  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, ctl, stream);
+  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, ctl, nullptr, nullptr, stream);
+}
+// ph_adamw_keep / ph_adamw_ctl with the exponential moving average of the weights updated in the same pass: see include/prismer_hip.h
+extern "C" int ph_adamw_ema(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1, float beta2,
+                            float eps, float weight_decay, float grad_scale, int zero_grad, const uint32_t* keep_bitmap, const ph_clip_ctl* ctl,
+                            float* ema, const float* ema_w, hipStream_t stream) {
+  PH_CHECK_ARG(ema && ema_w, "ph_adamw_ema: need the average and its weight (both in device memory)");
+  return adamw_launch(p, g, m, v, p_bf16, n, hyper, beta1, beta2, eps, weight_decay, grad_scale, zero_grad, keep_bitmap, ctl, ema, ema_w, stream);
 }
 extern "C" int ph_adamw(float* p, float* g, float* m, float* v, void* p_bf16, int64_t n, const float* hyper, float beta1,
                         float beta2, float eps, float weight_decay, float grad_scale, int zero_grad, hipStream_t stream) {
@@ -656,6 +698,31 @@ __global__ __launch_bounds__(256) void copy_bytes_kernel(u32x4* __restrict__ d, 
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (int64_t)gridDim.x * 256) d[i] = s[i];
 }
 }  // namespace
+namespace {
+// a <-> b through registers: every thread owns its vectors, so no temporary and no ordering between threads
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  const int64_t n4 = n >> 2;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 ta = reinterpret_cast<f32x4*>(a)[i], tb = reinterpret_cast<f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = tb;
+    reinterpret_cast<f32x4*>(b)[i] = ta;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const int64_t i = (n4 << 2) + threadIdx.x;
+    const float ta = a[i];
+    a[i] = b[i];
+    b[i] = ta;
+  }
+}
+}  // namespace
+extern "C" int ph_swap_f32(float* a, float* b, int64_t n, hipStream_t stream) {
+  PH_CHECK_ARG(a && b && n > 0 && ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0, "ph_swap_f32: need two 16-B aligned ranges of n >= 1 floats");
+  PH_CHECK_ARG((uintptr_t)a + 4 * (uintptr_t)n <= (uintptr_t)b || (uintptr_t)b + 4 * (uintptr_t)n <= (uintptr_t)a, "ph_swap_f32: the ranges overlap");
+  ProfScope prof__(PH_FAM_MISC, 0.0, 0.0, stream, "ph_swap_f32");
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, stream, a, b, n);
+  PH_LAUNCH_CHECK("swap_f32_kernel");
+  return PH_OK;
+}
 extern "C" int ph_fill_zero(void* p, int64_t bytes, hipStream_t stream) {
   PH_CHECK_ARG(p && bytes > 0 && (bytes % 16) == 0 && (((uintptr_t)p) & 15) == 0, "ph_fill_zero: need a 16-B aligned buffer of a multiple of 16 bytes");
   ProfScope prof__(PH_FAM_MISC, 0.0, 0.0, stream, "ph_fill_zero");

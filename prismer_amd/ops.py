@@ -945,6 +945,22 @@ def adamw_ctl(p, g, m, v, p_bf16, n, hyper, ctl, beta1=0.9, beta2=0.999, eps=1e-
                            weight_decay, grad_scale, int(zero_grad), ptr(keep), ptr(ctl), _stream()), 'ph_adamw_ctl')
 
 
+def adamw_ema(p, g, m, v, p_bf16, n, hyper, ema, ema_w, ctl=None, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.05, grad_scale=1.0, zero_grad=False,
+              keep=None):
+    """adamw / adamw_ctl (ctl given) with the moving average of the weights updated in the same launch (ph_adamw_ema): ema += ema_w[0] * (p' - ema),
+    ema fp32 [>= n], ema_w one fp32 on the device (1 - decay of this update); a skipped update (ctl.apply == 0) leaves ema alone"""
+    assert keep is None or keep.numel() * 32 * 1024 >= n
+    assert ema.dtype == F32 and ema.is_contiguous() and ema.numel() >= n and ema_w.dtype == F32 and ema_w.numel() >= 1 and ema_w.device == ema.device
+    check(lib.ph_adamw_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), ptr(p_bf16), n, hyper.data_ptr(), beta1, beta2, eps,
+                           weight_decay, grad_scale, int(zero_grad), ptr(keep), ptr(ctl), ema.data_ptr(), ema_w.data_ptr(), _stream()), 'ph_adamw_ema')
+
+
+def swap_f32(a, b):
+    """a <-> b for two contiguous, disjoint, 16-B aligned fp32 tensors of one length (ph_swap_f32): exact, no temporary"""
+    assert a.dtype == F32 and b.dtype == F32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    check(lib.ph_swap_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), 'ph_swap_f32')
+
+
 def cast_to_bf16(x, out=None, scale=1.0):
     if out is None:
         out = torch.empty(x.shape, dtype=BF16, device=x.device)

@@ -88,13 +88,70 @@ def guarded_step_spec(params, grads, m, v, applied, lr, betas=(0.9, 0.999), eps=
     return total, True, t
 
 
+def ema_decay_at(u, decay, warmup=False):
+    """decay of the weight average at update u (0-based schedule position: the index the LR schedule gets, skipped updates counted):
+    min(decay, (1 + u) / (10 + u)) with warm-up -- TensorFlow's ExponentialMovingAverage(num_updates=) / timm's ModelEmaV3 ramp: 0.1, 2/11,
+    3/12, ... so that the first updates are not averaged against the initial weights for 1 / (1 - decay) steps -- else `decay`"""
+    return min(float(decay), (1.0 + u) / (10.0 + u)) if warmup else float(decay)
+
+
+def ema_update_spec(ema, p_new, w):
+    """The specification of Trainer(ema_decay=) as plain tensor code: one update of the average, e' = e + w (p' - e) in fp32 with the product
+    and the sum contracted into one fma (what torch.lerp(e, p', w) computes for w < 0.5 -- the call of torch.optim.swa_utils.get_ema_multi_avg_fn
+    and timm.utils.ModelEma -- and what the compiler makes of the kernel's expression).  `w`: 1 - decay, evaluated in float64 by the caller
+    and rounded to fp32 here, as the word the step ships to the device is.
+    This is NOT the plain fp32 expression `ema + w * (p_new - ema)` with its product rounded on its own: that one is not bit-equal to torch.lerp
+    (about 5 % of the elements differ in the last bit at w = 0.1, torch's CPU kernel contracts), and of the two -- the plain expression or
+    equality with the call torch's and timm's EMA utilities make -- the specification keeps the second.  Both forms hold the error bar of
+    tests/test_ema_cpu.py against float64.  (The fma is formed in float64: the product of two fp32 values is exact there; the double rounding
+    of the sum can differ from a true fp32 fma only on an exact tie of the float64 result.)"""
+    w32 = torch.tensor(float(w), dtype=torch.float64).to(F32)
+    e = ema.to(F32)
+    return (w32.double() * (p_new.to(F32) - e).double() + e.double()).to(F32)
+
+
+def check_ema_options(ema_decay=None, ema_warmup=False, shard_optimizer=False, side_stream=False, micro_batches=1):
+    """argument validation of Trainer(ema_decay=, ema_warmup=), before anything is built; returns (decay or None, warmup)"""
+    if ema_decay is None:
+        if ema_warmup:
+            raise ValueError('ema_warmup=True needs ema_decay (the warm-up ramps the decay of the weight average up to it)')
+        return None, False
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, float) or not (0.0 < ema_decay < 1.0):          # (NaN fails the comparison too)
+        raise ValueError(f'ema_decay must be a float with 0 < ema_decay < 1 or None, got {ema_decay!r}')
+    if shard_optimizer:
+        raise ValueError('ema_decay with shard_optimizer is not supported (every rank updates a slice of the masters: the average would need '
+                         'the slices of the other ranks, or one more collective behind the sharded tails)')
+    if side_stream and micro_batches > 1:
+        raise ValueError('ema_decay with the eager micro_batches experiment is not supported')
+    return float(ema_decay), bool(ema_warmup)
+
+
+def _refuse_in_ema_scope(tr, what):
+    # (getattr: tests/test_accum_logic_cpu.py drives step() on a stand-in object that has no such attribute)
+    if getattr(tr, '_ema_scope', False):
+        raise RuntimeError(f'Trainer.{what} inside `with ema_weights()`: the masters hold the weight average there; leave the scope first')
+
+
 class Trainer:
     def __init__(self, model, lr=5e-5, weight_decay=0.05, betas=(0.9, 0.999), eps=1e-8, min_lr=0.0, total_steps=1000,
                  task='caption', use_graph=True, process_group=None, bucket_mb=64, side_stream=False, micro_batches=1, keep_grads=False,
                  max_text_len=None, grad_payload='fp32', transport='torch.distributed', dec_backward_stages=3, lr_schedule=None,
                  shard_optimizer=False, overwrite_single_writer=True, allow_eager_fallback=False, broadcast_buffers=False, exchange_issue='device',
-                 accum_steps=1, max_grad_norm=None, skip_nonfinite=False):
-        """max_grad_norm=c, skip_nonfinite=True: protection of the optimizer state, decided ON THE DEVICE inside the captured step (the host cannot: by
+                 accum_steps=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+        """ema_decay=d (a float, 0 < d < 1), ema_warmup=False: an exponential moving average of the TRAINABLE master weights, the weights one evaluates
+        and ships (timm.utils.ModelEma, torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn), kept in one fp32 buffer per store and updated by
+        the AdamW launch itself (ops.adamw_ema: the new master value is in a register there; +8 B/parameter of traffic on 30, no extra launch).
+        Specification: ema_decay_at / ema_update_spec above -- after every APPLIED update e <- e + (1 - d_u)(p' - e) with d_u = d, or
+        min(d, (1 + u) / (10 + u)) with ema_warmup, u = the 0-based schedule position of the update (`it - 1`, skipped updates counted).  The
+        average starts from the masters the Trainer was built on (after the rank-0 broadcast with N ranks), an update the guard skips leaves it
+        alone, accum_steps=k moves it with the closing micro-step only, and N ranks (plain all-reduce exchange) hold the same bits.  Frozen
+        parameters are not averaged (they never move), nor are BatchNorm running statistics (running means already).  Read-outs:
+        ema_state_dict() (a model.state_dict()-shaped dict of clones: the average where a parameter is trainable, the live value elsewhere),
+        `with trainer.ema_weights():` (masters <-> average swapped in place, bf16 shadows and derived buffers refreshed: eval forward, generate
+        and model.state_dict() see the average; the exit swaps back bit for bit; step() / state_dict() / load_state_dict() are refused
+        inside), state_dict()['ema'].  Refused with shard_optimizer and with the eager micro_batches experiment.
+
+        max_grad_norm=c, skip_nonfinite=True: protection of the optimizer state, decided ON THE DEVICE inside the captured step (the host cannot: by
         the time it could look at a loss the update has happened).  Specification: guarded_update_spec / guarded_step_spec above.  With g = the
         update gradient (flat buffers x _post_scale(): the mean over ranks and over an accumulation group) and total_norm = ||g||_2 over the trainable
         ranges of both stores, max_grad_norm=c makes AdamW see g * min(1, c / (total_norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_ in front of
@@ -143,6 +200,8 @@ class Trainer:
                              'would need one more collective in front of the sharded tails)')
         if self.guard and side_stream and micro_batches > 1:
             raise ValueError('max_grad_norm / skip_nonfinite with the eager micro_batches experiment are not supported')
+        self.ema_decay, self.ema_warmup = check_ema_options(ema_decay, ema_warmup, shard_optimizer, side_stream, micro_batches)
+        self._ema_scope = False                # inside `with ema_weights()`: the masters hold the average
         self.model = model
         self.enc, self.dec = model.expert_encoder, model.text_decoder
         self.init_lr, self.min_lr, self.total_steps = lr, min_lr, total_steps
@@ -199,6 +258,14 @@ class Trainer:
         self.v = [torch.zeros(max(hi - lo, 1), dtype=F32, device=dev) for lo, hi in own]
         self.piece_state = {}                                  # rs_ag: (store index, a, b) -> (m, v)
         self.hyper = torch.zeros(3, dtype=F32, device=dev)
+        # weight average: one fp32 buffer per store over the trainable range, and the word w = 1 - decay of the coming update IN FRONT of the
+        # three hyper words, so that the one ph_store_words launch of _host_prologue writes [w, lr (, bias corrections)] as one run.  Off:
+        # neither exists and `hyper` is the tensor it always was.
+        self.ema, self._step_words, self._ema_w = None, None, None
+        if self.ema_decay is not None:
+            self._step_words = torch.zeros(4, dtype=F32, device=dev)
+            self._ema_w, self.hyper = self._step_words[0:1], self._step_words[1:4]
+            self.ema = [st.master[:max(st.n_train, 1)].clone() for st in self.stores]
         # guarded update: control block (clip coefficient, apply flag, norm, applied / skipped counters -- Adam's t lives THERE, the host writes
         # hyper[0] only) and the per-block partials of the norm, both allocated once (nothing is allocated or zeroed inside the captured step)
         self.ctl = ops.ClipCtl(dev) if self.guard else None
@@ -277,6 +344,13 @@ class Trainer:
         for mod in (self.enc, self.dec):
             for b in mod.buffers():
                 torch.distributed.broadcast(b, 0, group=self.pg)
+        self._ema_reset()                                      # every rank's average starts from rank 0's weights
+
+    def _ema_reset(self):
+        """average <- masters (construction, after the rank-0 broadcast, a checkpoint without an average)"""
+        if getattr(self, 'ema', None) is not None:
+            for st, e in zip(self.stores, self.ema):
+                e.copy_(st.master[:e.numel()])
 
     def sync_buffers(self):
         """rank 0's BatchNorm running statistics and num_batches_tracked -> every rank (DDP's _sync_module_buffers before each forward), two
@@ -551,7 +625,11 @@ class Trainer:
 
     def _adamw(self, i):
         st = self.stores[i]
-        if self.guard:
+        if self.ema is not None:
+            ops.adamw_ema(st.master, st.grad, self.m[i], self.v[i], st.shadow, st.n_train, self.hyper, self.ema[i], self._ema_w,
+                          self.ctl if self.guard else None, self.betas[0], self.betas[1], self.eps, self.wd, self._post_scale(),
+                          zero_grad=not self.keep_grads, keep=self._keep_maps[i] if self._keep_maps else None)
+        elif self.guard:
             ops.adamw_ctl(st.master, st.grad, self.m[i], self.v[i], st.shadow, st.n_train, self.hyper, self.ctl, self.betas[0], self.betas[1],
                           self.eps, self.wd, self._post_scale(), zero_grad=not self.keep_grads, keep=self._keep_maps[i] if self._keep_maps else None)
         else:
@@ -844,10 +922,14 @@ class Trainer:
         # guarded update: the bias corrections follow the count of APPLIED updates, which only the device knows (ph_clip_finalize writes them)
         # (getattr: tests/test_accum_logic_cpu.py drives this method on a stand-in object that predates the guard and has no such attribute)
         hyper = (lr,) if getattr(self, 'guard', False) else (lr, 1.0 - self.betas[0] ** self.it, 1.0 - self.betas[1] ** self.it)
+        dst = self.hyper
+        if getattr(self, 'ema_decay', None) is not None:
+            # weight of the average for THIS update, in front of the hyper words (one buffer: still one launch); 1 - d in float64, fp32 on the way
+            dst, hyper = self._step_words, (1.0 - ema_decay_at(self.it - 1, self.ema_decay, self.ema_warmup),) + hyper
         if 'obj_detection' in self.enc.experts:
-            ops.store_words(self.hyper, hyper, self.table, [random.randint(0, 127) for _ in range(256)])
+            ops.store_words(dst, hyper, self.table, [random.randint(0, 127) for _ in range(256)])
         else:
-            ops.store_words(self.hyper, hyper)
+            ops.store_words(dst, hyper)
 
     # ------------------------------------------------------------------------------------------ public API
     def set_batch(self, experts, input_ids, attention_mask, labels, weights=None):
@@ -975,7 +1057,8 @@ class Trainer:
                     rng=random.getstate(), grads=[st.grad.clone() for st in self.stores], clean=self._grads_clean,
                     pieces={k: (m.clone(), v.clone()) for k, (m, v) in self.piece_state.items()},
                     micro=self._micro, step_open=self._step_open, loss_acc=self._loss_acc.clone(), group_loss=self._group_loss.clone(),
-                    ctl=self.ctl.words.clone() if self.guard else None, hyper=self.hyper.clone())
+                    ctl=self.ctl.words.clone() if self.guard else None, hyper=self.hyper.clone(),
+                    ema=[t.clone() for t in self.ema] if self.ema is not None else None)
 
     def _restore(self, snap):
         for st, t in zip(self.stores, snap['master']):
@@ -997,6 +1080,9 @@ class Trainer:
         self._loss_acc.copy_(snap['loss_acc']); self._group_loss.copy_(snap['group_loss'])
         if self.guard:
             self.ctl.words.copy_(snap['ctl']); self.hyper.copy_(snap['hyper'])
+        if self.ema is not None:
+            for dst, src in zip(self.ema, snap['ema']):
+                dst.copy_(src)
         random.setstate(snap['rng'])
 
     def _capture(self):
@@ -1092,6 +1178,7 @@ class Trainer:
     def step(self):
         """one optimisation step on the bound batch; returns the (device) scalar loss tensor without synchronising."""
         assert self.static is not None, 'call set_batch() first'
+        _refuse_in_ema_scope(self, 'step()')
         if self.use_graph and self.graphs is None:
             try:
                 self._capture()
@@ -1178,13 +1265,66 @@ class Trainer:
         self._micro = (self._micro + 1) % self.accum
         return self.loss_buf if self.accum == 1 or not self.use_graph else self._kind_loss[kind]
 
+    # ------------------------------------------------------------------------------------------ weight average (ema_decay=)
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f'Trainer.{what} needs a weight average: build the Trainer with ema_decay=')
+
+    def ema_state_dict(self):
+        """model.state_dict()-shaped dict of CLONES with the weight average in place of every trainable parameter; frozen parameters and
+        buffers (BatchNorm running statistics: running means already, not averaged) are the live model's.  Outside and inside ema_weights()."""
+        self._need_ema('ema_state_dict()')
+        avg = [st.master[:e.numel()] for st, e in zip(self.stores, self.ema)] if self._ema_scope else self.ema
+        spans = [(st.master.data_ptr(), st.n_train, a) for st, a in zip(self.stores, avg)]
+        out = {}
+        for k, t in self.model.state_dict().items():
+            t = t.detach()
+            for base, n, a in spans:                           # (parameters are views of the flat masters: found by address, so tied names resolve too)
+                off = (t.data_ptr() - base) // 4
+                if t.dtype == F32 and t.is_cuda and 0 <= off and off + t.numel() <= n and base <= t.data_ptr():
+                    t = a[off:off + t.numel()].view(t.shape)
+                    break
+            out[k] = t.clone()
+        return out
+
+    def _swap_ema(self):
+        for st, e in zip(self.stores, self.ema):
+            if st.n_train:
+                ops.swap_f32(st.master[:st.n_train], e[:st.n_train])
+                ops.cast_to_bf16(st.master[:st.n_train], st.shadow[:st.n_train])
+            st.refresh_derived()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """inside the scope the model IS the averaged model: masters and average are exchanged in place over the trainable ranges (ops.swap_f32:
+        exact, no temporary), bf16 shadows and derived buffers are refreshed, so model(..., train=False), generate and model.state_dict() see
+        the average.  The exit exchanges back and refreshes again: masters, shadows and derived buffers return bit for bit, captured graphs
+        stay valid (same buffers).  step() / state_dict() / load_state_dict() are refused inside; not re-entrant; refused inside an open
+        accumulation group."""
+        self._need_ema('ema_weights()')
+        _refuse_in_ema_scope(self, 'ema_weights()')
+        if self._micro:
+            raise RuntimeError(f'Trainer.ema_weights() inside an open accumulation group (micro_index = {self._micro} of accum_steps = {self.accum}): '
+                               'close or abort the group first')
+        self._swap_ema()
+        self._ema_scope = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_scope = False
+
     def state_dict(self):
         """model + optimizer + RNG: what `accelerator.save_state` writes (train_caption.py:174; the reference itself only ever reloads
-        the model weights, train_caption.py:103-108).  With shard_optimizer the Adam moments are this rank's slice."""
+        the model weights, train_caption.py:103-108).  With shard_optimizer the Adam moments are this rank's slice.  With ema_decay the weight
+        average (`ema`: one fp32 tensor per store) and, for the record, the decay it was kept with (`ema_decay`: a constructor option, which
+        load_state_dict does not restore -- it warns when the checkpoint's differs from the Trainer's)."""
         if self._micro:
             raise RuntimeError(f'Trainer.state_dict() inside an open accumulation group (micro_index = {self._micro} of accum_steps = {self.accum}): '
                                'the partial gradient sums are not part of a checkpoint; save at a group boundary (micro_index == 0)')
-        return dict(it=self.it, applied=self.applied_updates, skipped=self.skipped_updates, m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
+        _refuse_in_ema_scope(self, 'state_dict()')
+        ema = dict(ema=[t.clone() for t in self.ema], ema_decay=self.ema_decay) if self.ema is not None else {}
+        return dict(**ema, it=self.it, applied=self.applied_updates, skipped=self.skipped_updates, m=[t.clone() for t in self.m], v=[t.clone() for t in self.v],
                     model={k: t.detach().clone() for k, t in self.model.state_dict().items()},      # (state_dict() aliases the live buffers)
                     seed=self.seed.clone(), rng=random.getstate(), world=self.world,
                     shard_optimizer='rs_ag' if self.rs_ag else self.shard,
@@ -1195,18 +1335,32 @@ class Trainer:
         them, Adam moments, iteration counter (LR schedule position), dropout seed and Python RNG (instance-embedding draws).  Captured
         graphs stay valid: they reference the buffers, not their contents.  The applied-update count (Adam's t) is restored into a guarded
         Trainer; an unguarded one applies every update and keeps t = it."""
+        _refuse_in_ema_scope(self, 'load_state_dict()')
         mine = 'rs_ag' if self.rs_ag else self.shard
         if (sd.get("shard_optimizer", False) or False) != mine or ((self.shard or self.rs_ag) and sd.get("world", 1) != self.world):
             raise ValueError('Trainer.load_state_dict: optimizer sharding of the checkpoint '
                              f"(shard_optimizer={sd.get('shard_optimizer')}, world={sd.get('world')}) differs from this Trainer's")
         if len(sd['m']) != len(self.m) or any(a.shape != b.shape for a, b in zip(sd['m'] + sd['v'], self.m + self.v)):
             raise ValueError('Trainer.load_state_dict: Adam moment buffers do not match this model / freeze configuration')
+        ema = sd.get('ema') if self.ema is not None else None      # (a Trainer without an average ignores the checkpoint's)
+        if ema is not None and (len(ema) != len(self.ema) or any(a.shape != b.shape for a, b in zip(ema, self.ema))):
+            raise ValueError('Trainer.load_state_dict: the weight average of the checkpoint does not match this model / freeze configuration')
         self.model.load_state_dict(sd['model'], strict=strict)
         for st in self.stores:
             st.refresh()
         for dst, src in zip(self.m + self.v, list(sd['m']) + list(sd['v'])):
             dst.copy_(src)
         self.piece_state = {k: (m.to(self.device).clone(), v.to(self.device).clone()) for k, (m, v) in sd.get('pieces', {}).items()}
+        if ema is not None:
+            if sd.get('ema_decay', self.ema_decay) != self.ema_decay:
+                # the decay is a constructor option (like lr or betas), not state: the loaded average simply continues at THIS Trainer's decay
+                import warnings
+                warnings.warn(f"Trainer.load_state_dict: the checkpoint's weight average was kept with ema_decay={sd['ema_decay']!r}, this Trainer "
+                              f'continues it with ema_decay={self.ema_decay!r}')
+            for dst, src in zip(self.ema, ema):
+                dst.copy_(src)
+        else:
+            self._ema_reset()                                   # a checkpoint without an average: it starts from the loaded masters
         self.it = int(sd['it'])
         if self.guard:
             # Adam's t: a checkpoint without the key (written before the guard existed, every update applied) loads with applied = it.  The
