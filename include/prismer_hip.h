@@ -248,6 +248,23 @@ int ph_attention_bwd(const ph_attn_bwd_args* args, hipStream_t stream);
  * registers.  small_query_kernels = 0 forces the streaming kernels for every launch (A/B, tests), 1 restores the default, 2 = default without
  * the head-resident kernels, < 0 only queries.  Returns the previous setting. */
 int ph_attention_tuning(int small_query_kernels);
+/* Grouped cross-attention (training on n texts per image): `group` consecutive query rows share the K / V of one batch row.  f.B = R query
+ * rows; q / o / dO / dq / lse (and the dropout generator rows (r*H + h)*Sq + i) are indexed by r, k / v / dk / dv by r / group with their own
+ * batch strides.  The result of row r is what ph_attention_fwd / ph_attention_bwd give on K / V tiled to R rows; dk / dv of a batch row are the
+ * sum over its `group` query rows.  group >= 1, R % group == 0, no causal cut, no key mask: anything else is PH_ERR_BAD_ARG before any launch.
+ * dh = 64, Sq <= 32, Sk <= 320, group <= 16 run on the grouped kernels: forward one block per (row, head) reading the image's K / V; backward
+ * ONE launch, block = (image, head), dK / dV summed over the members in fp32 registers in member order and rounded once (no atomics: bitwise
+ * reproducible).  Every other shape, and every shape after ph_attention_tuning(0), runs the ungrouped kernels on K / V tiled into `ws` and
+ * folds the per-row dK / dV over the members in fp32: ph_attention_group_ws_bytes() is what `ws` must hold then (0 = not needed). */
+typedef struct { ph_attn_fwd_args f; int group; void* ws; int64_t ws_bytes; } ph_attn_group_fwd_args;
+typedef struct { ph_attn_bwd_args b; int group; void* ws; int64_t ws_bytes; } ph_attn_group_bwd_args;
+int64_t ph_attention_group_ws_bytes(const ph_attn_fwd_args* f, int group, int backward);
+int ph_attention_group_fwd(const ph_attn_group_fwd_args* args, hipStream_t stream);
+int ph_attention_group_bwd(const ph_attn_group_bwd_args* args, hipStream_t stream);
+/* Which directions may take the grouped kernels: bit 0 forward, bit 1 backward (default 3); a direction switched off runs the tiled route
+ * -- with the small-query kernels where the shape has them -- for A/B runs (tools/group_probe.py).  < 0 only queries.  Returns the previous
+ * setting. */
+int ph_attention_group_tuning(int kernels);
 /* Shared-prefix attention, forward only (rank inference: model/prismer_caption.py:59-112, model/prismer_vqa.py:64-113).  Row r of
  * R continuation rows (queries and keys t = 0 .. Tc-1) attends to two key segments:
  *   prefix keys 0 .. Tp-1 of prefix row r / group  (key_mask prefix_mask[(r/group)*pm_bs + j], no causal cut: the whole prefix

@@ -125,6 +125,14 @@ class AttnBwdArgs(C.Structure):
                 ('dv_bs', c_i64), ('dv_ts', c_i64), ('delta', c_void_p)]
 
 
+class AttnGroupFwdArgs(C.Structure):
+    _fields_ = [('f', AttnFwdArgs), ('group', c_int), ('ws', c_void_p), ('ws_bytes', c_i64)]
+
+
+class AttnGroupBwdArgs(C.Structure):
+    _fields_ = [('b', AttnBwdArgs), ('group', c_int), ('ws', c_void_p), ('ws_bytes', c_i64)]
+
+
 class AttnPrefixFwdArgs(C.Structure):
     _fields_ = [('q', c_void_p), ('pk', c_void_p), ('pv', c_void_p), ('ck', c_void_p), ('cv', c_void_p), ('o', c_void_p),
                 ('q_bs', c_i64), ('q_ts', c_i64), ('pk_bs', c_i64), ('pk_ts', c_i64), ('pv_bs', c_i64), ('pv_ts', c_i64),
@@ -193,6 +201,10 @@ _SIGS = {
     'ph_attention_fwd': (c_int, [C.POINTER(AttnFwdArgs), c_void_p]),
     'ph_attention_bwd': (c_int, [C.POINTER(AttnBwdArgs), c_void_p]),
     'ph_attention_prefix_fwd': (c_int, [C.POINTER(AttnPrefixFwdArgs), c_void_p]),
+    'ph_attention_group_fwd': (c_int, [C.POINTER(AttnGroupFwdArgs), c_void_p]),
+    'ph_attention_group_bwd': (c_int, [C.POINTER(AttnGroupBwdArgs), c_void_p]),
+    'ph_attention_group_ws_bytes': (c_i64, [C.POINTER(AttnFwdArgs), c_int, c_int]),
+    'ph_attention_group_tuning': (c_int, [c_int]),
     'ph_patchify': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ph_resize_bilinear_nchw_to_nhwc': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ph_gather_rows_bf16': (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_int, c_void_p]),

@@ -1382,23 +1382,23 @@ __device__ __forceinline__ void sm_fwd_merge_store(char* smem, int nunits, int n
   }
 }
 
+// Body of the small-query forward for query row b and head h; kb = the batch row K / V (and the key mask) are read from: b itself in
+// attn_fwd_small_kernel, b / group in attn_group_fwd_kernel (the text rows of an image share its K / V).  Generator rows and lse are indexed by b.
 template <int QT>
-__global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a) {
+__device__ __forceinline__ void sm_fwd_body(const ph_attn_fwd_args& a, int b, int kb, int h, char* smem_raw) {
   constexpr int DH = 64;
   using C = Cfg<DH>;
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 15, g = lane >> 4;
-  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
   const int nunits = (a.Sk + 31) >> 5, rows_pad = nunits * 32;
   bf16* vimg = reinterpret_cast<bf16*>(smem_raw);
   float* kst = reinterpret_cast<float*>(vimg + rows_pad * C::RS);
   const bf16* Q = reinterpret_cast<const bf16*>(a.q) + b * a.q_bs + (int64_t)h * DH;
-  const bf16* K = reinterpret_cast<const bf16*>(a.k) + b * a.k_bs + (int64_t)h * DH;
-  const bf16* V = reinterpret_cast<const bf16*>(a.v) + b * a.v_bs + (int64_t)h * DH;
+  const bf16* K = reinterpret_cast<const bf16*>(a.k) + kb * a.k_bs + (int64_t)h * DH;
+  const bf16* V = reinterpret_cast<const bf16*>(a.v) + kb * a.v_bs + (int64_t)h * DH;
   bf16* O = reinterpret_cast<bf16*>(a.o) + b * a.o_bs + (int64_t)h * DH;
   float* lse = a.lse ? a.lse + (int64_t)(b * a.H + h) * a.Sq : nullptr;
-  const uint8_t* km = a.key_mask ? a.key_mask + (int64_t)b * a.Sk : nullptr;
+  const uint8_t* km = a.key_mask ? a.key_mask + (int64_t)kb * a.Sk : nullptr;
 
   int qi[QT];
   bf16x8 qf[QT][C::KS];
@@ -1447,6 +1447,23 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a)
   }
   if (nunits == 1) sm_fwd_store_single<QT>(qi, a.Sq, m, lsum, o, O, a.o_ts, lse);       // (self-attention at T <= 32)
   else sm_fwd_merge_store<QT>(smem_raw, nunits, a.Sq, m, lsum, o, O, a.o_ts, lse);
+}
+
+template <int QT>
+__global__ __launch_bounds__(256) void attn_fwd_small_kernel(ph_attn_fwd_args a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
+  sm_fwd_body<QT>(a, b, b, h, smem_raw);
+}
+
+// Grouped cross-attention forward (training on n texts per image): block = (text row r, head h), K / V of image r / group.  The `group` blocks of
+// an image re-read its K / V from L2, as the shared-prefix kernel below does; everything a row computes is what attn_fwd_small_kernel computes
+// for it on K / V tiled to R rows, bit for bit (same unit order, same merge, same generator rows).
+template <int QT>
+__global__ __launch_bounds__(256) void attn_group_fwd_kernel(ph_attn_group_fwd_args ga) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int r = blockIdx.x / ga.f.H, h = blockIdx.x % ga.f.H;
+  sm_fwd_body<QT>(ga.f, r, r / ga.group, h, smem_raw);
 }
 
 // Shared-prefix forward (rank inference, model/prismer_caption.py:59-112 and model/prismer_vqa.py:64-113 without the k-fold tiling): attn_fwd_small_kernel
@@ -1785,6 +1802,316 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(ph_attn_bwd_args a)
   }
 }
 
+// Grouped cross-attention backward (training on n texts per image): block = (image, head).  The K image, the key states and the V row fragments
+// of the image are set up ONCE; the block then walks the image's `group` text rows in member order, each member through the sweeps of
+// attn_bwd_small_kernel (same P / dP, same dropout words: generator row (r*H + h)*Sq + i of text row r, same dQ merge), and keeps dK^T / dV^T of
+// its waves' key units in fp32 registers ACROSS the members: dK / dV of the image are the member sum in fp32, in member order, rounded to bf16
+// once and stored once -- no per-row dK / dV in memory, no fold pass, no atomics (bitwise reproducible).
+// LDS: K image | dQ merge images (their own region: the K image lives through all members) | Q, dO images of the current member | per-wave
+// transposition scratch | key states | delta | delta partials.  Sk = 320: 46080 + 34816 + 9216 + 18432 + 1280 + 640 = 110464 B, one block per CU.
+__host__ __device__ inline int sm_gbwd_bytes(int rows_pad) {
+  return rows_pad * Cfg<64>::RS * 2 + 4 * 32 * SM_OS * 4 + 2 * 32 * Cfg<64>::RS * 2 + 4 * 2 * 32 * SM_TS * 2 + rows_pad * 4 + (1 + 4) * 32 * 4;
+}
+// KT3: 16-key tiles of a wave's THIRD unit (keys 256 ..) that exist: 0 for Sk <= 256, 1 for Sk <= 272 (the 260 image tokens), else 2 -- their
+// dK^T / dV^T accumulators are the registers the kernel is short of (32 per tile).
+template <int KT3> __host__ __device__ constexpr int ui_nt(int ui) { return ui < 2 ? 2 : KT3; }   // live 16-key tiles of a wave's unit ui
+template <int KT3>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void attn_group_bwd_kernel(ph_attn_group_bwd_args ga) {
+  constexpr int DH = 64, QT = 2, NQ = 32;
+  using C = Cfg<DH>;
+  const ph_attn_bwd_args& a = ga.b;
+  const ph_attn_fwd_args& f = a.f;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int img = blockIdx.x / f.H, h = blockIdx.x % f.H;
+  const int nunits = (f.Sk + 31) >> 5, rows_pad = nunits * 32;
+  bf16* kimg = reinterpret_cast<bf16*>(smem_raw);
+  float* dqbuf = reinterpret_cast<float*>(kimg + rows_pad * C::RS);
+  bf16* qimg = reinterpret_cast<bf16*>(dqbuf + 4 * NQ * SM_OS);
+  bf16* doimg = qimg + NQ * C::RS;
+  bf16* tsc = doimg + NQ * C::RS + wave * (2 * 32 * SM_TS);  // this wave's scratch: P~ [32 keys][SM_TS], dS [32 keys][SM_TS]
+  float* kst = reinterpret_cast<float*>(doimg + NQ * C::RS + 4 * 2 * 32 * SM_TS);
+  float* delta_s = kst + rows_pad;
+  float* dpart = delta_s + NQ;                               // [4][NQ]
+  const bf16* K = reinterpret_cast<const bf16*>(f.k) + img * f.k_bs + (int64_t)h * DH;
+  const bf16* V = reinterpret_cast<const bf16*>(f.v) + img * f.v_bs + (int64_t)h * DH;
+
+  // ---- per image: K image, key states (no key mask: a key is live or beyond Sk)
+  sm_stage<SM_MAX_UNITS>(kimg, K, f.k_ts, f.Sk, rows_pad);
+  for (int i = threadIdx.x; i < rows_pad; i += 256) kst[i] = key_state(1u, i, f.Sk);
+  DropCtx dc;
+  const bool drop = f.drop_p > 0.f;
+  if (drop) dc = make_drop(f.drop_seed, f.drop_stream, f.drop_p);
+  const float pscale = drop ? dc.scale : 1.f;
+  f32x4 dka[SM_MAXU][2][C::DT], dva[SM_MAXU][2][C::DT];      // dK^T / dV^T of this wave's keys, summed over the members
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui)
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+      for (int d = 0; d < C::DT; ++d) { dka[ui][kt][d] = f32x4{0.f, 0.f, 0.f, 0.f}; dva[ui][kt][d] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+
+  for (int j = 0; j < ga.group; ++j) {
+    // the per-lane indices are re-derived per member from an opaque copy: as loop invariants, the ~150 LDS / global offsets computed from them
+    // are hoisted in front of the loop and spilled (seen in the ISA: 150 scratch stores ahead of the loop, as many reloads per member)
+    int lane_j = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane_j));
+    const int lane = lane_j, c = lane & 15, g = lane >> 4;
+    const int r = img * ga.group + j;
+    const bf16* Q = reinterpret_cast<const bf16*>(f.q) + r * f.q_bs + (int64_t)h * DH;
+    const bf16* dO = reinterpret_cast<const bf16*>(a.d_o) + r * a.do_bs + (int64_t)h * DH;
+    const float* lse_base = f.lse + (int64_t)(r * f.H + h) * f.Sq;
+    int qi[QT];
+    uint32_t ridx[QT];
+    bf16x8 qf[QT][C::KS], dof[QT][C::KS];
+    float lse[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      qi[t] = t * 16 + c;
+      const int qr = qi[t] < f.Sq ? qi[t] : f.Sq - 1;
+#pragma unroll
+      for (int ks = 0; ks < C::KS; ++ks) {
+        qf[t][ks] = *reinterpret_cast<const bf16x8*>(Q + (int64_t)qr * f.q_ts + ks * 32 + g * 8);
+        dof[t][ks] = *reinterpret_cast<const bf16x8*>(dO + (int64_t)qr * a.do_ts + ks * 32 + g * 8);
+      }
+      ridx[t] = (uint32_t)((r * f.H + h) * f.Sq + qr);
+      lse[t] = lse_base[qr];
+    }
+    if (j) __syncthreads();                                  // the previous member's Q / dO images and dQ merge images are dead
+    sm_stage<(NQ * 8 + 255) / 256>(qimg, Q, f.q_ts, f.Sq, NQ);
+    sm_stage<(NQ * 8 + 255) / 256>(doimg, dO, a.do_ts, f.Sq, NQ);
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+#pragma unroll
+      for (int ks = 0; ks < C::KS; ++ks) { settle(qf[t][ks]); settle(dof[t][ks]); }
+      settle(lse[t]);
+    }
+    __syncthreads();
+
+    // ---- sweep 0 (as attn_bwd_small_kernel)
+    f32x4 pu[SM_MAXU][QT][2], du[SM_MAXU][QT][2];
+    uint32_t keepu[SM_MAXU][QT];
+    float dsum[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) dsum[t] = 0.f;
+#pragma unroll
+    for (int ui = 0; ui < SM_MAXU; ++ui) {
+      if ((ui < 2 || KT3 > 0) && wave + 4 * ui < nunits) {
+        const int kbase = (wave + 4 * ui) * 32;
+        // V row fragments of the unit (A operands of dP^T = V dO^T) from L2: not held across the members, the registers carry dK^T / dV^T
+        bf16x8 vf[2][C::KS];
+        const int NT = ui_nt<KT3>(ui);                        // (keys of a tile beyond it do not exist: P = 0 exactly, nothing to add)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          const int kr = min(kbase + nt * 16 + c, f.Sk - 1);
+#pragma unroll
+          for (int ks = 0; ks < C::KS; ++ks) vf[nt][ks] = *reinterpret_cast<const bf16x8*>(V + (int64_t)kr * f.v_ts + ks * 32 + g * 8);
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          f32x4 acc[QT], dp[QT];
+#pragma unroll
+          for (int t = 0; t < QT; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+          for (int ks = 0; ks < C::KS; ++ks) {
+            const bf16x8 kfr = frag_rows<DH>(kimg, kbase + nt * 16, ks, lane);
+#pragma unroll
+            for (int t = 0; t < QT; ++t) {
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, qf[t][ks], acc[t], 0, 0, 0);
+              dp[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[nt][ks], dof[t][ks], dp[t], 0, 0, 0);
+            }
+          }
+          const f32x4 st = *reinterpret_cast<const f32x4*>(kst + kbase + nt * 16 + g * 4);
+#pragma unroll
+          for (int t = 0; t < QT; ++t) {
+            u32x4 rnd = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
+            if (drop) rnd = philox4x32((uint32_t)((kbase + nt * 16 + g * 4) >> 2), ridx[t], dc.stream, 0xa77eu, dc.k0, dc.k1);
+            if (nt == 0) keepu[ui][t] = 0u;
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const float p = __expf(score_of(acc[t][rr], f.scale, st[rr], false) - lse[t]);
+              const bool keep = !drop || (rnd[rr] >> 8) >= dc.thr;
+              const float dpe = drop ? (keep ? dp[t][rr] * dc.scale : 0.f) : dp[t][rr];
+              keepu[ui][t] |= keep ? (1u << (nt * 4 + rr)) : 0u;
+              pu[ui][t][nt][rr] = p;
+              du[ui][t][nt][rr] = dpe;
+              dsum[t] += p * dpe;
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      const float v = xor_sum(dsum[t]);
+      if (g == 0) dpart[wave * NQ + t * 16 + c] = v;           // (0 from a wave without units)
+    }
+    __syncthreads();
+    if (threadIdx.x < NQ) delta_s[threadIdx.x] = dpart[threadIdx.x] + dpart[NQ + threadIdx.x] + dpart[2 * NQ + threadIdx.x] + dpart[3 * NQ + threadIdx.x];
+    __syncthreads();
+    float delta[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) delta[t] = delta_s[t * 16 + c];
+
+    // ---- sweep 1: dQ of this member; dK^T / dV^T accumulate over the members
+    f32x4 dq[QT][C::DT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+#pragma unroll
+      for (int d = 0; d < C::DT; ++d) dq[t][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ui = 0; ui < SM_MAXU; ++ui) {
+      if ((ui < 2 || KT3 > 0) && wave + 4 * ui < nunits) {
+        const int kbase = (wave + 4 * ui) * 32;
+        bf16x8 dsf[QT];
+#pragma unroll
+        for (int t = 0; t < QT; ++t) {
+          f32x4 ds[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+          for (int nt = 0; nt < ui_nt<KT3>(ui); ++nt)
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const float p = pu[ui][t][nt][rr];
+              const float dsv = p * (du[ui][t][nt][rr] - delta[t]);
+              ds[nt][rr] = dsv;
+              const float pdrop = ((keepu[ui][t] >> (nt * 4 + rr)) & 1u) ? p * pscale : 0.f;
+              const int key = nt * 16 + g * 4 + rr;
+              tsc[key * SM_TS + t * 16 + c] = f2bf(qi[t] < f.Sq ? pdrop : 0.f);
+              tsc[32 * SM_TS + key * SM_TS + t * 16 + c] = f2bf(qi[t] < f.Sq ? dsv : 0.f);
+            }
+          dsf[t] = pack2(ds[0], ds[1]);
+        }
+#pragma unroll
+        for (int d = 0; d < C::DT; ++d) {
+          const bf16x8 kfr = frag_tr<DH>(kimg, kbase, d * 16, lane);
+#pragma unroll
+          for (int t = 0; t < QT; ++t) dq[t][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr, dsf[t], dq[t][d], 0, 0, 0);
+        }
+        // (the wave's own LDS writes above are ordered before these reads: same wave, in-order LDS pipe)
+#pragma unroll
+        for (int kt = 0; kt < ui_nt<KT3>(ui); ++kt) {
+          const bf16* row = tsc + (kt * 16 + c) * SM_TS + 4 * g;
+          const bf16x4 p0 = *reinterpret_cast<const bf16x4*>(row), p1 = *reinterpret_cast<const bf16x4*>(row + 16);
+          const bf16x4 s0 = *reinterpret_cast<const bf16x4*>(row + 32 * SM_TS), s1 = *reinterpret_cast<const bf16x4*>(row + 32 * SM_TS + 16);
+          bf16x8 pf, sf;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { pf[e] = p0[e]; pf[4 + e] = p1[e]; sf[e] = s0[e]; sf[4 + e] = s1[e]; }
+#pragma unroll
+          for (int d = 0; d < C::DT; ++d) {
+            const bf16x8 dfr = frag_tr<DH>(doimg, 0, d * 16, lane);
+            const bf16x8 qfr = frag_tr<DH>(qimg, 0, d * 16, lane);
+            dva[ui][kt][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dfr, pf, dva[ui][kt][d], 0, 0, 0);
+            dka[ui][kt][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qfr, sf, dka[ui][kt][d], 0, 0, 0);
+          }
+        }
+      }
+    }
+    // ---- dQ of this member: one unit -> wave 0 holds all of it; otherwise merged over the waves through LDS
+    if (nunits == 1) {
+      if (wave == 0) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t)
+          if (qi[t] < f.Sq) {
+            bf16* dQ = reinterpret_cast<bf16*>(a.dq) + r * a.dq_bs + (int64_t)qi[t] * a.dq_ts + (int64_t)h * DH;
+#pragma unroll
+            for (int d = 0; d < C::DT; ++d) {
+              const bf16x4 tt = {f2bf(dq[t][d][0] * f.scale), f2bf(dq[t][d][1] * f.scale), f2bf(dq[t][d][2] * f.scale), f2bf(dq[t][d][3] * f.scale)};
+              *reinterpret_cast<bf16x4*>(dQ + d * 16 + g * 4) = tt;
+            }
+          }
+      }
+    } else {
+      if (wave < nunits) {
+#pragma unroll
+        for (int t = 0; t < QT; ++t)
+#pragma unroll
+          for (int d = 0; d < C::DT; ++d) *reinterpret_cast<f32x4*>(dqbuf + (wave * NQ + t * 16 + c) * SM_OS + d * 16 + g * 4) = dq[t][d];
+      }
+      __syncthreads();
+      const int q = threadIdx.x >> 2, col = (threadIdx.x & 3) * 16;
+      if (q < f.Sq && q < NQ) {
+        const int nw = nunits < 4 ? nunits : 4;
+        float acc[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        for (int w = 0; w < nw; ++w) {
+          const float* src = dqbuf + (w * NQ + q) * SM_OS + col;
+#pragma unroll
+          for (int j4 = 0; j4 < 4; ++j4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src + j4 * 4);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) acc[j4 * 4 + rr] += v[rr];
+          }
+        }
+        bf16* dQ = reinterpret_cast<bf16*>(a.dq) + r * a.dq_bs + (int64_t)q * a.dq_ts + (int64_t)h * DH + col;
+        bf16x8 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { o0[e] = f2bf(acc[e] * f.scale); o1[e] = f2bf(acc[8 + e] * f.scale); }
+        *reinterpret_cast<bf16x8*>(dQ) = o0;
+        *reinterpret_cast<bf16x8*>(dQ + 8) = o1;
+      }
+    }
+  }
+  // ---- dK / dV of the image: the member sums, rounded once
+#pragma unroll
+  for (int ui = 0; ui < SM_MAXU; ++ui) {
+    if ((ui < 2 || KT3 > 0) && wave + 4 * ui < nunits) {
+#pragma unroll
+      for (int kt = 0; kt < ui_nt<KT3>(ui); ++kt) {
+        const int kk = (wave + 4 * ui) * 32 + kt * 16 + c;
+        if (kk < f.Sk) {
+          bf16* dK = reinterpret_cast<bf16*>(a.dk) + img * a.dk_bs + (int64_t)kk * a.dk_ts + (int64_t)h * DH;
+          bf16* dV = reinterpret_cast<bf16*>(a.dv) + img * a.dv_bs + (int64_t)kk * a.dv_ts + (int64_t)h * DH;
+#pragma unroll
+          for (int d = 0; d < C::DT; ++d) {
+            const f32x4 k4 = dka[ui][kt][d], v4 = dva[ui][kt][d];
+            const bf16x4 tk = {f2bf(k4[0] * f.scale), f2bf(k4[1] * f.scale), f2bf(k4[2] * f.scale), f2bf(k4[3] * f.scale)};
+            const bf16x4 tv = {f2bf(v4[0]), f2bf(v4[1]), f2bf(v4[2]), f2bf(v4[3])};
+            *reinterpret_cast<bf16x4*>(dK + d * 16 + g * 4) = tk;
+            *reinterpret_cast<bf16x4*>(dV + d * 16 + g * 4) = tv;
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---- the route outside the grouped kernels: K / V tiled to one copy per text row, the ungrouped kernels, dK / dV folded over the members.
+// dst[r][s][0..W) = src row r / group, token s (16-B chunks; W = H * dh)
+__global__ __launch_bounds__(256) void attn_group_tile_kernel(const bf16* src, int64_t bs, int64_t ts, bf16* dst, int R, int group, int Sk, int W) {
+  const int cpr = W >> 3;
+  const int64_t n = (int64_t)R * Sk * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int ch = (int)(i % cpr);
+    const int64_t rs = i / cpr;
+    const int s = (int)(rs % Sk), r = (int)(rs / Sk);
+    *reinterpret_cast<u32x4*>(dst + rs * W + ch * 8) = *reinterpret_cast<const u32x4*>(src + (r / group) * bs + s * ts + ch * 8);
+  }
+}
+// dst token (b, s) = bf16(sum over the members j, in member order, of the bf16 rows [b*group + j][s] in fp32)
+__global__ __launch_bounds__(256) void attn_group_fold_kernel(const bf16* rows, bf16* dst, int64_t bs, int64_t ts, int Bi, int group, int Sk, int W) {
+  const int cpr = W >> 3;
+  const int64_t n = (int64_t)Bi * Sk * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int ch = (int)(i % cpr);
+    const int64_t bs_i = i / cpr;
+    const int s = (int)(bs_i % Sk), b = (int)(bs_i / Sk);
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    for (int j = 0; j < group; ++j) {
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(rows + (((int64_t)b * group + j) * Sk + s) * W + ch * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += bf2f(v[e]);
+    }
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = f2bf(acc[e]);
+    *reinterpret_cast<bf16x8*>(dst + b * bs + s * ts + ch * 8) = o;
+  }
+}
+
 // eligibility of the small-query kernels: head dim 64, all queries of a (batch, head) pair in QT = 2 sub-tiles (Sq <= 32), K / V image within the LDS budget
 int attn_small_qt(const ph_attn_fwd_args* f) {
   if (f->dh != 64 || f->Sk > 32 * SM_MAX_UNITS) return 0;
@@ -1970,6 +2297,118 @@ extern "C" int ph_attention_bwd(const ph_attn_bwd_args* a, hipStream_t stream) {
 #undef PH_BWD
   PH_LAUNCH_CHECK("attn_bwd kernels");
   return PH_OK;
+}
+
+// ---- grouped cross-attention: `group` consecutive query rows share the K / V of batch row r / group
+namespace {
+constexpr int GROUP_MAX_FAST = 16;
+int g_attn_group = 3;      // bit 0: grouped forward kernel, bit 1: grouped backward kernel (ph_attention_group_tuning: A/B against the tiled route)
+bool attn_group_fast(const ph_attn_fwd_args* f, int group, bool backward) {
+  return (g_attn_small & 1) && (g_attn_group & (backward ? 2 : 1)) && attn_small_qt(f) == 2 && group <= GROUP_MAX_FAST;
+}
+int check_group(const ph_attn_fwd_args* f, int group, const char* who) {
+  PH_CHECK_ARG(f, "%s: null args", who);
+  PH_CHECK_ARG(group >= 1, "%s: group = %d (must be >= 1)", who, group);
+  PH_CHECK_ARG(f->B > 0 && f->B % group == 0, "%s: %d query rows are not a multiple of group = %d", who, f->B, group);
+  PH_CHECK_ARG(!f->causal && !f->key_mask, "%s: no causal cut and no key mask (cross-attention has neither)", who);
+  return check_fwd(f, who);
+}
+int64_t group_tile_elems(const ph_attn_fwd_args* f) { return (int64_t)f->B * f->Sk * f->H * f->dh; }
+void group_tile(const ph_attn_fwd_args* f, int group, const void* src, int64_t bs, int64_t ts, bf16* dst, hipStream_t stream) {
+  const int64_t n = group_tile_elems(f) / 8;
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(attn_group_tile_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const bf16*>(src), bs, ts, dst, f->B, group, f->Sk,
+                     f->H * f->dh);
+}
+}  // namespace
+
+extern "C" int64_t ph_attention_group_ws_bytes(const ph_attn_fwd_args* f, int group, int backward) {
+  if (!f || group < 1 || f->B <= 0 || f->H <= 0 || f->Sk <= 0 || f->dh <= 0) return 0;
+  if (attn_group_fast(f, group, backward != 0)) return 0;
+  return (backward ? 4 : 2) * group_tile_elems(f) * 2;
+}
+
+extern "C" int ph_attention_group_fwd(const ph_attn_group_fwd_args* a, hipStream_t stream) {
+  const char* who = "ph_attention_group_fwd";
+  PH_CHECK_ARG(a, "%s: null args", who);
+  int rc = check_group(&a->f, a->group, who);
+  if (rc) return rc;
+  const ph_attn_fwd_args& f = a->f;
+  if (attn_group_fast(&f, a->group, false)) {
+    ProfScope prof__(PH_FAM_ATTN_FWD, 4.0 * f.B * (double)f.H * f.Sq * (double)f.Sk * f.dh, 0.0, stream);
+    const int rows_pad = ceil_div(f.Sk, 32) * 32;
+    const int smem = set_smem(attn_group_fwd_kernel<2>, sm_fwd_bytes(rows_pad, sm_merge_bytes<2>()));
+    hipLaunchKernelGGL((attn_group_fwd_kernel<2>), dim3(f.B * f.H), dim3(256), smem, stream, *a);
+    PH_LAUNCH_CHECK("attn_group_fwd_kernel");
+    return PH_OK;
+  }
+  // outside the grouped kernels: the ungrouped launch on K / V tiled to one copy per query row (same generator rows, same lse rows)
+  const int64_t ne = group_tile_elems(&f);
+  PH_CHECK_ARG(a->ws && a->ws_bytes >= 2 * ne * 2 && ((uintptr_t)a->ws & 15) == 0,
+               "%s: this shape runs on tiled K / V and needs ph_attention_group_ws_bytes() = %lld B of workspace", who, (long long)(2 * ne * 2));
+  bf16* kt = reinterpret_cast<bf16*>(a->ws);
+  bf16* vt = kt + ne;
+  group_tile(&f, a->group, f.k, f.k_bs, f.k_ts, kt, stream);
+  group_tile(&f, a->group, f.v, f.v_bs, f.v_ts, vt, stream);
+  PH_LAUNCH_CHECK("attn_group_tile_kernel");
+  ph_attn_fwd_args t = f;
+  const int64_t W = (int64_t)f.H * f.dh;
+  t.k = kt; t.v = vt;
+  t.k_bs = t.v_bs = f.Sk * W;
+  t.k_ts = t.v_ts = W;
+  return ph_attention_fwd(&t, stream);
+}
+
+extern "C" int ph_attention_group_bwd(const ph_attn_group_bwd_args* a, hipStream_t stream) {
+  const char* who = "ph_attention_group_bwd";
+  PH_CHECK_ARG(a, "%s: null args", who);
+  int rc = check_group(&a->b.f, a->group, who);
+  if (rc) return rc;
+  const ph_attn_bwd_args& b = a->b;
+  const ph_attn_fwd_args& f = b.f;
+  PH_CHECK_ARG(b.d_o && b.dq && b.dk && b.dv && f.lse, "%s: null pointer", who);
+  PH_CHECK_ARG(((b.do_ts | b.dq_ts | b.dk_ts | b.dv_ts | b.do_bs | b.dq_bs | b.dk_bs | b.dv_bs) % 8) == 0, "%s: strides must be multiples of 8", who);
+  PH_CHECK_ARG((((uintptr_t)b.d_o | (uintptr_t)b.dq | (uintptr_t)b.dk | (uintptr_t)b.dv) & 15) == 0, "%s: pointers must be 16-B aligned", who);
+  PH_CHECK_ARG((int64_t)f.Sq * b.do_ts < (1ll << 30), "%s: a (row, head) slice of dO must span < 2 GiB", who);
+  if (attn_group_fast(&f, a->group, true)) {
+    ProfScope prof__(PH_FAM_ATTN_BWD, 10.0 * f.B * (double)f.H * f.Sq * (double)f.Sk * f.dh, 0.0, stream);
+    const int rows_pad = ceil_div(f.Sk, 32) * 32;
+    const dim3 grid(f.B / a->group * f.H);
+#define PH_GBWD(KT3V) { const int smem = set_smem(attn_group_bwd_kernel<KT3V>, sm_gbwd_bytes(rows_pad));                      \
+                        hipLaunchKernelGGL((attn_group_bwd_kernel<KT3V>), grid, dim3(256), smem, stream, *a); }
+    if (f.Sk <= 256) PH_GBWD(0) else if (f.Sk <= 272) PH_GBWD(1) else PH_GBWD(2)
+#undef PH_GBWD
+    PH_LAUNCH_CHECK("attn_group_bwd_kernel");
+    return PH_OK;
+  }
+  const int64_t ne = group_tile_elems(&f);
+  PH_CHECK_ARG(a->ws && a->ws_bytes >= 4 * ne * 2 && ((uintptr_t)a->ws & 15) == 0,
+               "%s: this shape runs on tiled K / V and needs ph_attention_group_ws_bytes() = %lld B of workspace", who, (long long)(4 * ne * 2));
+  bf16* kt = reinterpret_cast<bf16*>(a->ws);
+  bf16 *vt = kt + ne, *dkr = kt + 2 * ne, *dvr = kt + 3 * ne;
+  group_tile(&f, a->group, f.k, f.k_bs, f.k_ts, kt, stream);
+  group_tile(&f, a->group, f.v, f.v_bs, f.v_ts, vt, stream);
+  PH_LAUNCH_CHECK("attn_group_tile_kernel");
+  ph_attn_bwd_args t = b;
+  const int64_t W = (int64_t)f.H * f.dh;
+  t.f.k = kt; t.f.v = vt; t.dk = dkr; t.dv = dvr;
+  t.f.k_bs = t.f.v_bs = t.dk_bs = t.dv_bs = f.Sk * W;
+  t.f.k_ts = t.f.v_ts = t.dk_ts = t.dv_ts = W;
+  rc = ph_attention_bwd(&t, stream);
+  if (rc) return rc;
+  const int Bi = f.B / a->group;
+  const int64_t n = (int64_t)Bi * f.Sk * (W / 8);
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(attn_group_fold_kernel, dim3(blocks), dim3(256), 0, stream, dkr, reinterpret_cast<bf16*>(b.dk), b.dk_bs, b.dk_ts, Bi, a->group, f.Sk, (int)W);
+  hipLaunchKernelGGL(attn_group_fold_kernel, dim3(blocks), dim3(256), 0, stream, dvr, reinterpret_cast<bf16*>(b.dv), b.dv_bs, b.dv_ts, Bi, a->group, f.Sk, (int)W);
+  PH_LAUNCH_CHECK("attn_group_fold_kernel");
+  return PH_OK;
+}
+
+extern "C" int ph_attention_group_tuning(int kernels) {
+  const int old = g_attn_group;
+  if (kernels >= 0) g_attn_group = kernels & 3;
+  return old;
 }
 
 extern "C" int ph_attention_tuning(int small_query_kernels) {

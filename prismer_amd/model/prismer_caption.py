@@ -3,6 +3,7 @@ import torch
 
 from .prismer import Prismer
 from .rank import rank_answers
+from ..trainer import check_text_rows
 
 
 def tile(x, dim, n_tile):
@@ -23,8 +24,11 @@ class PrismerCaption(Prismer):
         return t.input_ids, t.attention_mask
 
     def forward(self, experts, caption=None, answer=None, train=True, prefix='', inference='generate', k_test=32, return_scores=False, sample=None,
-                generate_args=None):
-        """sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
+                generate_args=None, texts_per_image=1):
+        """texts_per_image=n (training): `caption` holds n captions per image, image-major (captions b*n .. b*n+n-1 describe image b: the order
+        generate(num_return_sequences=n) returns).  The encoder runs once per image; the decoder's cross-attention shares an image's K/V among
+        its n rows instead of reading an n-fold tiled encoder output.  The loss is the mean over the B*n rows.
+        sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
         num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences captions, image-major.
         generate_args: None, or a dict of further arguments of `text_decoder.generate` for the beam search (repetition_penalty,
         no_repeat_ngram_size); the `sample` dict carries them for sampled decoding."""
@@ -39,6 +43,7 @@ class PrismerCaption(Prismer):
             elif len(prefix) > 0:
                 plen = len(self._tokenize(prefix).input_ids) - 1 if self.tokenizer is not None else self.prompt_length
                 answer_targets[:, :plen] = -100
+            check_text_rows(experts_train.shape[0], input_ids.shape[0], texts_per_image, 'PrismerCaption.forward')
             out = self.text_decoder(input_ids, attention_mask=attention_mask, encoder_hidden_states=experts_train, labels=answer_targets,
                                     return_dict=True)
             return out.loss.mean()

@@ -3,6 +3,7 @@ import torch
 
 from .prismer import Prismer
 from .rank import rank_answers
+from ..trainer import check_text_rows
 
 
 class PrismerVQA(Prismer):
@@ -15,8 +16,11 @@ class PrismerVQA(Prismer):
         return t.input_ids, t.attention_mask
 
     def forward(self, experts, question, answer=None, weights=None, train=True, inference='rank', k_test=128, return_scores=False, sample=None,
-                generate_args=None):
-        """sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
+                generate_args=None, texts_per_image=1):
+        """texts_per_image=n (training): `question`, `answer` and `weights` hold n entries per image, image-major (entries b*n .. b*n+n-1 belong
+        to image b).  The encoder runs once per image and the decoder's cross-attention shares an image's K/V among its n rows; the loss is the
+        mean of weights * loss over the B*n rows.
+        sample: None = the reference's fixed beam search; a dict of sampling arguments of `text_decoder.generate` (top_p, top_k, temperature,
         num_return_sequences, seed) routes inference='generate' through sampled decoding: B * num_return_sequences answers, image-major.
         generate_args: None, or a dict of further arguments of `text_decoder.generate` for the beam search (repetition_penalty,
         no_repeat_ngram_size); the `sample` dict carries them for sampled decoding."""
@@ -38,6 +42,7 @@ class PrismerVQA(Prismer):
             attention_mask = torch.cat([q_att, a_att], dim=1)
             targets = input_ids.masked_fill(input_ids == pad, -100)
             targets[:, :-a_ids.shape[1]] = -100                                           # prismer_vqa.py:32-33
+            check_text_rows(enc.shape[0], input_ids.shape[0], texts_per_image, 'PrismerVQA.forward')
             out = self.text_decoder(input_ids, attention_mask=attention_mask, encoder_hidden_states=enc, labels=targets, return_dict=True)
             return (weights.to(out.loss.dtype) * out.loss).mean()                           # prismer_vqa.py:40-41
         with torch.no_grad():

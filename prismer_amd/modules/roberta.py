@@ -195,12 +195,14 @@ class RobertaForCausalLMModified(nn.Module):
     def forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, labels=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None):
         from .. import ops
+        enc = encoder_hidden_states
+        # n texts per image: Bi encoder rows serve Bi*n text rows (image-major); the autograd backward returns d(enc) with Bi rows
+        DecoderProgram.texts_per_image(input_ids.shape[0], enc.shape[0])
         if not input_ids.is_cuda:
             raise RuntimeError('prismer_amd.RobertaForCausalLMModified runs on the MI355X HIP path only.')
         prog = self._program()
         if not getattr(self._store, 'managed', False):
             self._store.refresh_if_stale()
-        enc = encoder_hidden_states
         if enc.dtype != torch.bfloat16:
             enc = ops.cast_to_bf16(enc.contiguous().float())
         enc = enc.contiguous()

@@ -514,6 +514,51 @@ def attention_bwd(d_o, q, k, v, o, lse, B, H, Sq, Sk, dh, *, q_strides, k_stride
     check(lib.ph_attention_bwd(C.byref(a), _stream()), 'ph_attention_bwd')
 
 
+def _group_ws(g, f, group, backward, device):
+    """workspace of a grouped launch outside the grouped kernels (tiled K / V, per-row dK / dV); None on the grouped kernels"""
+    nbytes = lib.ph_attention_group_ws_bytes(C.byref(f), group, int(backward))
+    if nbytes <= 0:
+        return None
+    ws = torch.empty(nbytes // 2, dtype=BF16, device=device)
+    g.ws, g.ws_bytes = ws.data_ptr(), nbytes
+    return ws
+
+
+def attention_group_fwd(q, k, v, R, group, H, Sq, Sk, dh, *, q_strides, k_strides, v_strides, drop=None, out=None):
+    """cross-attention of R query rows, `group` consecutive rows per K/V batch row (ph_attention_group_fwd): q [R][Sq], k / v [R // group][Sk],
+    strides as attention_fwd.  Returns (o [R*Sq, H*dh] bf16, lse [R*H*Sq] fp32): what attention_fwd gives on K/V tiled to R rows."""
+    if out is None:
+        out = torch.empty((R * Sq, H * dh), dtype=BF16, device=q.device)
+    lse = torch.empty((R * H * Sq,), dtype=F32, device=q.device)
+    o_strides = (Sq * H * dh, H * dh)
+    g = _lib.AttnGroupFwdArgs()
+    g.f = _attn_args(q, k, v, out, R, H, Sq, Sk, dh, (q_strides, k_strides, v_strides, o_strides), dh ** -0.5, None, False, drop, lse)
+    g.group = group
+    ws = _group_ws(g, g.f, group, False, q.device)
+    check(lib.ph_attention_group_fwd(C.byref(g), _stream()), 'ph_attention_group_fwd')
+    del ws
+    return out, lse
+
+
+def attention_group_bwd(d_o, q, k, v, o, lse, R, group, H, Sq, Sk, dh, *, q_strides, k_strides, v_strides, dq, dk, dv, dq_strides,
+                        dk_strides, dv_strides, drop=None):
+    """backward of attention_group_fwd: dq [R][Sq]; dk / dv [R // group][Sk] = the sum over a K/V row's `group` query rows"""
+    g = _lib.AttnGroupBwdArgs()
+    a = g.b
+    o_strides = (Sq * H * dh, H * dh)
+    a.f = _attn_args(q, k, v, o, R, H, Sq, Sk, dh, (q_strides, k_strides, v_strides, o_strides), dh ** -0.5, None, False, drop, lse)
+    a.d_o = d_o.data_ptr()
+    a.do_bs, a.do_ts = o_strides
+    a.dq, a.dk, a.dv = dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    (a.dq_bs, a.dq_ts), (a.dk_bs, a.dk_ts), (a.dv_bs, a.dv_ts) = dq_strides, dk_strides, dv_strides
+    delta = torch.empty((R * H * Sq,), dtype=F32, device=q.device)
+    a.delta = delta.data_ptr()
+    g.group = group
+    ws = _group_ws(g, a.f, group, True, q.device)
+    check(lib.ph_attention_group_bwd(C.byref(g), _stream()), 'ph_attention_group_bwd')
+    del ws
+
+
 def attention_prefix_fwd(q, pk, pv, ck, cv, R, H, Tc, Tp, group, dh, *, q_strides, pk_strides, pv_strides, ck_strides, cv_strides,
                          prefix_mask=None, pm_stride=0, cont_mask=None, cm_stride=0, out=None):
     """shared-prefix attention (ph_attention_prefix_fwd): continuation row r (queries / keys q, ck, cv: [R][Tc]) against the Tp

@@ -114,7 +114,8 @@ class DecoderProgram:
         blk['qkv'].wgrad(dqkv, s['h'])
         return blk['qkv'].dgrad(dqkv, residual=ds)
 
-    def cross_attn_fwd(self, blk, li, h, hf, enc, B, T, S, seed, sv, kv=None, kv_ready=None):
+    def cross_attn_fwd(self, blk, li, h, hf, enc, B, T, S, seed, sv, kv=None, kv_ready=None, n=1):
+        """n > 1: the B text rows are n per image (image-major); enc / kv hold B // n images and row r reads the K/V of image r // n"""
         d = self.d
         H, nh = d.hidden_size, d.num_attention_heads
         dh = H // nh
@@ -125,7 +126,10 @@ class DecoderProgram:
             torch.cuda.current_stream().wait_event(kv_ready)       # the K/V projections ran on the branch stream
         ks = (S * kv.stride(0), kv.stride(0))                      # kv may be a column slice of the all-layers buffer
         dr_a = self.drop(li * 16 + 3, d.attention_probs_dropout_prob, seed)
-        o, lse = ops.attention_fwd(q, kv[:, :H], kv[:, H:], B, nh, T, S, dh, q_strides=(T * H, H), k_strides=ks, v_strides=ks, drop=dr_a)
+        if n > 1:
+            o, lse = ops.attention_group_fwd(q, kv[:, :H], kv[:, H:], B, n, nh, T, S, dh, q_strides=(T * H, H), k_strides=ks, v_strides=ks, drop=dr_a)
+        else:
+            o, lse = ops.attention_fwd(q, kv[:, :H], kv[:, H:], B, nh, T, S, dh, q_strides=(T * H, H), k_strides=ks, v_strides=ks, drop=dr_a)
         dr_h = self.drop(li * 16 + 4, d.hidden_dropout_prob, seed)
         s = blk['out'].fwd(o, drop=dr_h, residual=hf, out_f32=True)
         y, yf, m, r = self.post_ln(blk['ln'], s)
@@ -133,8 +137,8 @@ class DecoderProgram:
             sv.append(dict(h=h, q=q, kv=kv, o=o, lse=lse, s=s, m=m, r=r, dr_a=dr_a, dr_h=dr_h))
         return y, yf
 
-    def cross_attn_bwd(self, blk, s, dy, enc, denc, B, T, S, dkv=None):
-        """dkv: this layer's column slice of the all-layers dK/dV buffer (merged projection: its dgrad / wgrad run once,
+    def cross_attn_bwd(self, blk, s, dy, enc, denc, B, T, S, dkv=None, n=1):
+        """n > 1: n text rows per image, dK / dV (and dkv, enc, denc) have B // n image rows: the member sum.  dkv: this layer's column slice of the all-layers dK/dV buffer (merged projection: its dgrad / wgrad run once,
         after the last layer); None: per-layer K/V linear, d(enc) accumulated into the fp32 buffer `denc`."""
         d = self.d
         H, nh = d.hidden_size, d.num_attention_heads
@@ -148,9 +152,12 @@ class DecoderProgram:
             dkv = torch.empty(s['kv'].shape, dtype=BF16, device=dy.device)
         kv = s['kv']
         ks, dks = (S * kv.stride(0), kv.stride(0)), (S * dkv.stride(0), dkv.stride(0))
-        ops.attention_bwd(do, s['q'], kv[:, :H], kv[:, H:], s['o'], s['lse'], B, nh, T, S, dh, q_strides=(T * H, H), k_strides=ks,
-                          v_strides=ks, dq=dq, dk=dkv[:, :H], dv=dkv[:, H:], dq_strides=(T * H, H), dk_strides=dks, dv_strides=dks,
-                          drop=s['dr_a'])
+        kw = dict(q_strides=(T * H, H), k_strides=ks, v_strides=ks, dq=dq, dk=dkv[:, :H], dv=dkv[:, H:], dq_strides=(T * H, H), dk_strides=dks,
+                  dv_strides=dks, drop=s['dr_a'])
+        if n > 1:
+            ops.attention_group_bwd(do, s['q'], kv[:, :H], kv[:, H:], s['o'], s['lse'], B, n, nh, T, S, dh, **kw)
+        else:
+            ops.attention_bwd(do, s['q'], kv[:, :H], kv[:, H:], s['o'], s['lse'], B, nh, T, S, dh, **kw)
         blk['q'].wgrad(dq, s['h'])
         if not merged:
             blk['kv'].wgrad(dkv, enc)
@@ -254,16 +261,26 @@ class DecoderProgram:
         ops.gemm(t1, P.w('roberta.embeddings.word_embeddings.weight'), out=logits, bias=P.f('lm_head.bias'), N=d.vocab_size)
         return logits, (dict(t0pre=t0pre, t0=t0, t1=t1, hm=hm, hr=hr) if keep else None)
 
+    @staticmethod
+    def texts_per_image(rows, images):
+        """n of a batch of `rows` text rows on `images` encoder rows"""
+        if images <= 0 or rows % images != 0:
+            raise ValueError(f'decoder: {rows} text rows cannot be shared out over {images} encoder rows (text rows must be a multiple of the images)')
+        return rows // images
+
     def forward(self, input_ids, attention_mask, enc, labels, seed, save, want_logits=True):
-        """enc: [B, S, Hv] bf16 contiguous. seed: int64[1] device tensor or None (no dropout = eval mode).
-        Returns (logits_buf [B*T, Vpad] bf16, loss [B] fp32 or None, saved)."""
+        """enc: [Bi, S, Hv] bf16 contiguous, B % Bi == 0: n = B // Bi text rows per image, image-major (text rows b*n .. b*n+n-1 belong to
+        image b).  The K/V projections run on the Bi*S encoder rows; the cross-attention of row r reads image r // n.  seed: int64[1] device
+        tensor or None (no dropout = eval mode).  Returns (logits_buf [B*T, Vpad] bf16, loss [B] fp32 or None, saved)."""
         d = self.d
         B, T = input_ids.shape
+        n = self.texts_per_image(B, enc.shape[0])
+        Bi = B // n
         S = enc.shape[1]
         H, nh = d.hidden_size, d.num_attention_heads
         input_ids = input_ids.contiguous()
         key_mask = self._key_mask(attention_mask)
-        enc2 = enc.reshape(B * S, enc.shape[2])
+        enc2 = enc.reshape(Bi * S, enc.shape[2])
         sv = [] if save else None
         dr_e = self.drop(9000, d.hidden_dropout_prob, seed)
         h, xhat, erstd, hf = self._embed(input_ids, dr_e)
@@ -276,7 +293,7 @@ class DecoderProgram:
                                      key_mask=key_mask, causal=True, drop=dr_a) + (dr_a,)
 
         def cross(i, blk, h, hf):
-            return self.cross_attn_fwd(blk, i, h, hf, enc2, B, T, S, seed, sv, kvs[i], kv_evs[i])
+            return self.cross_attn_fwd(blk, i, h, hf, enc2, B, T, S, seed, sv, kvs[i], kv_evs[i], n=n)
         h, hf = self._layers(h, hf, attend, cross, seed, sv)
         logits, head = self._lm_head(h, True)
         loss = row_lse = None
@@ -285,7 +302,7 @@ class DecoderProgram:
             loss, row_lse = ops.ce_fwd(logits, labels, B, T, d.vocab_size, d.label_smoothing)
         saved = None
         if save:
-            saved = dict(blocks=sv, B=B, T=T, S=S, ids=input_ids, key_mask=key_mask, enc=enc2, xhat=xhat, erstd=erstd, dr_e=dr_e, hL=h,
+            saved = dict(blocks=sv, B=B, T=T, S=S, n=n, ids=input_ids, key_mask=key_mask, enc=enc2, xhat=xhat, erstd=erstd, dr_e=dr_e, hL=h,
                          logits=logits, labels=labels, row_lse=row_lse, **head)
         return logits, loss, saved
 
@@ -402,7 +419,7 @@ class DecoderProgram:
         return loss
 
     def backward(self, sv, dloss):
-        """dloss: fp32 [B] gradient of the per-sample losses. Returns d(enc) as bf16 [B, S, Hv]."""
+        """dloss: fp32 [B] gradient of the per-row losses. Returns d(enc) as bf16 [Bi, S, Hv] (Bi = B // n images: the sum over an image's rows)."""
         st = self.backward_start(sv, dloss)
         self.backward_layers(st, len(self.layers), 0)
         return self.backward_finish(st)
@@ -436,8 +453,9 @@ class DecoderProgram:
         H = d.hidden_size
         nl = len(self.layers)
         merged = self.kv_all is not None and nl > 0
-        denc = None if merged else ops.zeros((B * S, d.vision_hidden_size), F32, dh.device)
-        dkv_all = torch.empty(B * S, 2 * H * nl, dtype=BF16, device=dh.device) if merged else None
+        Bi = B // sv.get('n', 1)                                            # K/V, dK/dV and d(enc) are per image
+        denc = None if merged else ops.zeros((Bi * S, d.vision_hidden_size), F32, dh.device)
+        dkv_all = torch.empty(Bi * S, 2 * H * nl, dtype=BF16, device=dh.device) if merged else None
         F_ = self.final
         dh = self.mlp_bwd(F_['mlp'], blocks.pop(), dh)
         dh = self.self_attn_bwd(F_['sa'], blocks.pop(), dh, B, T, sv['key_mask'])
@@ -452,14 +470,14 @@ class DecoderProgram:
             dh = self.mlp_bwd(L['mlp'], blocks.pop(), dh)
             dh = self.adaptor_bwd(L['ad'], blocks.pop(), dh)
             dh = self.cross_attn_bwd(L['ca'], blocks.pop(), dh, sv['enc'], st['denc'], B, T, S,
-                                     dkv=st['dkv_all'][:, 2 * H * li:2 * H * (li + 1)] if merged else None)
+                                     dkv=st['dkv_all'][:, 2 * H * li:2 * H * (li + 1)] if merged else None, n=sv.get('n', 1))
             dh = self.self_attn_bwd(L['sa'], blocks.pop(), dh, B, T, sv['key_mask'])
         st['dh'] = dh
 
     def backward_finish(self, st):
         d, P = self.d, self.P
         sv, dh, merged, denc, dkv_all = st['sv'], st['dh'], st['merged'], st['denc'], st['dkv_all']
-        B, S = sv['B'], sv['S']
+        B, S = sv['B'] // sv.get('n', 1), sv['S']                          # image rows
         e = 'roberta.embeddings.'
         wname = e + 'word_embeddings.weight'
         # The tied word-embedding gradient has two writers, the LM-head wgrad GEMM (read-modify-write tiles) and these

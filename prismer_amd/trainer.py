@@ -126,6 +126,39 @@ def check_ema_options(ema_decay=None, ema_warmup=False, shard_optimizer=False, s
     return float(ema_decay), bool(ema_warmup)
 
 
+def check_texts_per_image(texts_per_image=1, side_stream=False, micro_batches=1):
+    """validated Trainer(texts_per_image=n): n >= 1 text rows per image.  Refused with the eager micro_batches experiment (it cuts images and
+    text rows with the same bounds)."""
+    n = int(texts_per_image)
+    if n != texts_per_image or n < 1:
+        raise ValueError(f'texts_per_image must be an integer >= 1, got {texts_per_image!r}')
+    if n > 1 and side_stream and micro_batches > 1:
+        raise ValueError('texts_per_image > 1 with the eager micro_batches experiment is not supported')
+    return n
+
+
+def check_text_rows(image_rows, text_rows, texts_per_image, what='set_batch'):
+    """image b owns text rows b*n .. b*n+n-1 (image-major, the order generate(num_return_sequences=n) returns)"""
+    if text_rows != image_rows * texts_per_image:
+        raise ValueError(f'{what}: {text_rows} text rows for {image_rows} images with texts_per_image = {texts_per_image} '
+                         f'(expected {image_rows * texts_per_image} rows, image-major: rows b*n .. b*n+n-1 belong to image b)')
+
+
+def dloss_rows(image_rows, texts_per_image, weights=None, device=None):
+    """d(total) / d(loss_r) of the R = Bi*n text rows: the total is the mean of the R row losses, or of weights * loss: 1/R, or weights_r / R"""
+    R = image_rows * texts_per_image
+    if weights is None:
+        return torch.full((R,), 1.0 / R, dtype=F32, device=device)
+    return weights.to(F32) / R
+
+
+def _image_rows(experts):
+    v = experts['rgb'] if 'rgb' in experts else next(iter(experts.values()))
+    while isinstance(v, dict):
+        v = next(iter(v.values()))
+    return v.shape[0]
+
+
 def _refuse_in_ema_scope(tr, what):
     # (getattr: tests/test_accum_logic_cpu.py drives step() on a stand-in object that has no such attribute)
     if getattr(tr, '_ema_scope', False):
@@ -137,8 +170,18 @@ class Trainer:
                  task='caption', use_graph=True, process_group=None, bucket_mb=64, side_stream=False, micro_batches=1, keep_grads=False,
                  max_text_len=None, grad_payload='fp32', transport='torch.distributed', dec_backward_stages=3, lr_schedule=None,
                  shard_optimizer=False, overwrite_single_writer=True, allow_eager_fallback=False, broadcast_buffers=False, exchange_issue='device',
-                 accum_steps=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False):
-        """ema_decay=d (a float, 0 < d < 1), ema_warmup=False: an exponential moving average of the TRAINABLE master weights, the weights one evaluates
+                 accum_steps=1, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, texts_per_image=1):
+        """texts_per_image=n >= 1: every image of the batch carries n text rows (COCO's 5 captions, VQAv2's questions, n sampled captions to
+        re-rank).  set_batch takes Bi images and Bi*n text rows, image-major (rows b*n .. b*n+n-1 belong to image b: the order
+        generate(num_return_sequences=n) returns); weights, when given, are per text row.  The step computes what the reference computes on the
+        encoder output tiled n times (repeat_interleave) -- the mean of the Bi*n row losses (of weights * loss) -- but runs the stems, the ViT, the
+        resampler, their backward and the merged cross-attention K/V projection ONCE per image: the cross-attention of row r reads the K/V of
+        image r // n (ops.attention_group_fwd / _bwd) and d(enc) of an image is the sum over its rows.  BatchNorm therefore sees the Bi images
+        once (batch statistics over Bi images; running statistics and counters move once per forward), instance embeddings are drawn once, the
+        decoder's dropout masks are those of an ordinary batch of Bi*n rows.  n = 1 is the step it was, launch for launch.  Composes with
+        accum_steps, max_grad_norm, skip_nonfinite, ema_decay and graph capture (static shapes); refused with the eager micro_batches experiment.
+
+        ema_decay=d (a float, 0 < d < 1), ema_warmup=False: an exponential moving average of the TRAINABLE master weights, the weights one evaluates
         and ships (timm.utils.ModelEma, torch.optim.swa_utils.AveragedModel + get_ema_multi_avg_fn), kept in one fp32 buffer per store and updated by
         the AdamW launch itself (ops.adamw_ema: the new master value is in a register there; +8 B/parameter of traffic on 30, no extra launch).
         Specification: ema_decay_at / ema_update_spec above -- after every APPLIED update e <- e + (1 - d_u)(p' - e) with d_u = d, or
@@ -182,6 +225,7 @@ class Trainer:
         the same.  Captured form: an opening micro-step (single-writer weight gradients overwritten), a middle one (everything accumulates) and a
         closing one (a middle micro-step + both AdamW launches), three graphs over ONE memory pool; accum_steps=1 is the single graph it was.
         N ranks: non-closing micro-steps exchange nothing (DDP's no_sync), the closing one runs the staged schedule on the accumulated sum."""
+        self.texts_per_image = check_texts_per_image(texts_per_image, side_stream, micro_batches)
         self.accum = int(accum_steps)
         if self.accum < 1:
             raise ValueError('accum_steps must be >= 1')
@@ -541,13 +585,17 @@ class Trainer:
         S, Mx = d.seq_len, d.num_expert_tokens
         h, xf, self.sv_f = ep.forward_front(s['experts'], self.table, True, True)
         B = s['input_ids'].shape[0]
-        parts = self._slices(B)
+        n = self.texts_per_image
+        parts = self._slices(B) if n == 1 else [(0, B)]
         self.sv_t, self.denc, self.dec_state, losses = [None] * len(parts), [None] * len(parts), [None] * len(parts), [None] * len(parts)
         dp.kv_prefetch = len(parts) == 1
         for mi, (b0, b1) in enumerate(parts):
             with (ops.MICRO.branch(mi) if len(parts) > 1 else contextlib.nullcontext()):
                 Bh = b1 - b0
-                enc_out, self.sv_t[mi] = ep.forward_trunk(h[b0 * S:b1 * S], None if xf is None else xf[b0 * Mx:b1 * Mx], Bh, True)
+                if n > 1:                                   # the encoder runs on the B // n images; text rows share its output n to one
+                    enc_out, self.sv_t[mi] = ep.forward_trunk(h, xf, B // n, True)
+                else:
+                    enc_out, self.sv_t[mi] = ep.forward_trunk(h[b0 * S:b1 * S], None if xf is None else xf[b0 * Mx:b1 * Mx], Bh, True)
                 dp.site_base = mi << 20
                 _, loss, sv_d = dp.forward(s['input_ids'][b0:b1], s['attention_mask'][b0:b1], enc_out, s['labels'][b0:b1], self.seed, True)
                 # caption: loss.mean() (prismer_caption.py:33); VQA: (weights * loss).mean() (prismer_vqa.py:40-41).  d(total)/d(loss_b) =
@@ -933,7 +981,9 @@ class Trainer:
 
     # ------------------------------------------------------------------------------------------ public API
     def set_batch(self, experts, input_ids, attention_mask, labels, weights=None):
-        """(re)binds the static input buffers. First call allocates them; later calls copy into them."""
+        """(re)binds the static input buffers. First call allocates them; later calls copy into them.  With texts_per_image = n the text tensors
+        (and weights) have n rows per image of `experts`, image-major."""
+        check_text_rows(_image_rows(experts), input_ids.shape[0], self.texts_per_image)
         for k, v in experts.items():                 # expert-map resolution fixes the program's token geometry
             if k != 'rgb':
                 er = (v.get('label_map', v.get('label', v.get('raw'))) if isinstance(v, dict) else v).shape[-1]
@@ -958,7 +1008,7 @@ class Trainer:
                                attention_mask=torch.zeros((B, T), dtype=attention_mask.dtype, device=self.device),
                                labels=torch.full((B, T), -100, dtype=labels.dtype, device=self.device),
                                weights=None if weights is None else torch.zeros(B, dtype=F32, device=self.device),
-                               dloss=torch.full((B,), 1.0 / B, dtype=F32, device=self.device))      # d(total) / d(loss_b): 1/B or weights_b / B
+                               dloss=dloss_rows(B // self.texts_per_image, self.texts_per_image, device=self.device))   # d(total) / d(loss_r): 1/R or weights_r / R
 
         self._bind(self.static, experts, input_ids, attention_mask, labels, weights)
 
@@ -1007,6 +1057,7 @@ class Trainer:
             raise RuntimeError('prefetch_batch: bind the first batch with set_batch (it fixes the shapes of the captured program)')
         if self._staged:
             raise RuntimeError('prefetch_batch: a staged batch is waiting for commit_prefetched() (one staging set: a second prefetch would overwrite it)')
+        check_text_rows(_image_rows(experts), input_ids.shape[0], self.texts_per_image, 'prefetch_batch')
         if self.staging is None:
             def clone(t):
                 return {k: clone(v) for k, v in t.items()} if isinstance(t, dict) else (None if t is None else t.clone())
