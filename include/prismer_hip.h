@@ -239,6 +239,9 @@ typedef struct {
   int64_t dq_bs, dq_ts, dk_bs, dk_ts, dv_bs, dv_ts;
   float* delta;                   /* workspace fp32 [B*H*Sq] */
 } ph_attn_bwd_args;
+/* A query row with no live key (every key excluded by key_mask): the forward is defined (the uniform mean of the Sk value rows), the
+ * gradients of such a row, and what it adds to dk / dv, are unspecified but finite -- its lse saturates at -FLT_MAX, so the recomputed
+ * p = exp(score - lse) is 1 instead of 1 / Sk.  No caller produces one: captions are right-padded and start with BOS. */
 int ph_attention_bwd(const ph_attn_bwd_args* args, hipStream_t stream);
 /* Kernel family selection (revision 103).  Launches with head dim 64, Sq <= 32 and Sk <= 320 -- the decoder's self- and cross-attention
  * (roberta.py:95-126 at T = 30 text tokens, 260 image tokens) -- run on the small-query kernels: one block per (batch, head), the keys split

@@ -496,7 +496,8 @@ ATTN_CASES = [  # B, H, Sq, Sk, dh, causal, masked, drop
     (2, 4, 40, 40, 64, True, True, 0.1),         # VQA text length (prismer_vqa.py:22-30): Sq > 32 -> the streaming kernels on both sides
     (2, 4, 30, 40, 64, True, True, 0.1),         # two key units over four waves (waves without a unit in the fused backward)
     (2, 4, 20, 80, 64, False, True, 0.1),        # three key units: the 3-unit forward merge (Sk 65..96)
-    (2, 3, 1, 23, 64, True, True, 0.0),          # one query: a cached decode step (generation)
+    (2, 3, 1, 23, 64, True, True, 0.0),          # one query, ONE live key (Sq = 1 under the causal cut drops every ki > 0): an edge, not a decode step --
+                                                 # the layout of a cached decode step is test_attention_rows_gpu.py::test_decode_layout
     (2, 2, 17, 320, 64, False, True, 0.2),       # the largest key image the small kernels take
     (1, 2, 64, 37, 64, False, False, 0.0),       # full 64-query tile, ragged keys (streaming kernels: Sq > 32)
     (2, 3, 280, 150, 64, False, False, 0.0),     # mask-free kernels, ragged tails on both sides

@@ -103,3 +103,115 @@ def splitmix64(z):
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
     return z ^ (z >> 31)
+
+
+# ---------------------------------------------------------------------------------------------- attention: per-row checks
+# A float64 reference, a float64 emulation that rounds where the bf16 kernels round, and a per-row metric.  Plain torch, any device.
+# Layout of every tensor: [B, H, S, dh]; every result is float64 (lse: [B, H, Sq]).
+def bf16_round64(x):
+    return x.to(torch.bfloat16).to(torch.float64)
+
+
+def attn_live(B, H, Sq, Sk, key_mask=None, causal=False, device='cpu'):
+    """bool [B, H, Sq, Sk]: the keys a query may see (attn_ref of test_kernels_gpu: tril for the causal cut, & key mask)"""
+    m = torch.ones(Sq, Sk, dtype=torch.bool, device=device)
+    if causal:
+        m = torch.tril(m)
+    m = m[None, None].expand(B, H, Sq, Sk).clone()
+    if key_mask is not None:
+        m &= key_mask.to(device).bool()[:, None, None, :]
+    return m
+
+
+def _attn_scores(q, k, scale, live):
+    s = q.double() @ k.double().transpose(-1, -2) * scale
+    return s.masked_fill(~live, torch.finfo(torch.float32).min)      # a row with no live key: uniform over the Sk keys, like attn_ref
+
+
+def _keep_scale(keep, p, like):
+    if keep is None:
+        return None
+    return keep.to(like.device).reshape(like.shape).double() / (1.0 - p)
+
+
+def attn_ref64(q, k, v, d_o, scale, key_mask=None, causal=False, keep=None, p=0.0, live=None):
+    """attn_ref in float64 on the values handed in (bf16-rounded by the caller), gradients in closed form.  `live` overrides the mask built
+    from key_mask / causal.  Returns dict(o, lse, dq, dk, dv); d_o = None leaves the gradients out.  Like autograd through masked_fill,
+    no gradient reaches an excluded score."""
+    B, H, Sq, _ = q.shape
+    Sk = k.shape[2]
+    if live is None:
+        live = attn_live(B, H, Sq, Sk, key_mask, causal, q.device)
+    s = _attn_scores(q, k, scale, live)
+    lse = torch.logsumexp(s, dim=-1)
+    pr = torch.softmax(s, dim=-1)                                    # (not exp(s - lse): lse of a row with no live key saturates at finfo.min)
+    ks = _keep_scale(keep, p, pr)
+    prd = pr if ks is None else pr * ks
+    out = dict(o=prd @ v.double(), lse=lse)
+    if d_o is None:
+        return out
+    d_o = d_o.double()
+    dp = d_o @ v.double().transpose(-1, -2)
+    if ks is not None:
+        dp = dp * ks
+    ds = pr * (dp - (pr * dp).sum(-1, keepdim=True)) * live
+    out.update(dq=ds @ k.double() * scale, dk=ds.transpose(-1, -2) @ q.double() * scale, dv=prd.transpose(-1, -2) @ d_o)
+    return out
+
+
+def attn_emulated(q, k, v, d_o, scale, key_mask=None, causal=False, keep=None, p=0.0, live=None):
+    """The operation of attn_ref64 in float64 with the roundings of a bf16 flash-attention kernel put in: P (after dropout) to bf16 before P V and
+    before P^T dO, o to bf16, delta = rowsum(dO * o) from the rounded o, lse to fp32 (the backward recomputes P from it), dS to bf16 before
+    dS K and dS^T Q, every output to bf16.  It says how far a correct kernel may be from attn_ref64 and never sees a kernel."""
+    B, H, Sq, _ = q.shape
+    Sk = k.shape[2]
+    if live is None:
+        live = attn_live(B, H, Sq, Sk, key_mask, causal, q.device)
+    s = _attn_scores(q, k, scale, live)
+    mx = s.max(-1, keepdim=True).values
+    pu = torch.exp(s - mx)                                           # unnormalised, <= 1: what goes into the P V product
+    lsum = pu.sum(-1, keepdim=True)
+    ks = _keep_scale(keep, p, pu)
+    o = bf16_round64((bf16_round64(pu if ks is None else pu * ks) @ v.double()) / lsum)
+    lse = (mx[..., 0] + torch.log(lsum[..., 0])).float().double()
+    out = dict(o=o, lse=lse)
+    if d_o is None:
+        return out
+    d_o = d_o.double()
+    pr = torch.exp(s - lse[..., None])
+    dv = bf16_round64(bf16_round64(pr if ks is None else pr * ks).transpose(-1, -2) @ d_o)
+    dp = d_o @ v.double().transpose(-1, -2)
+    if ks is not None:
+        dp = dp * ks
+    delta = (d_o * o).sum(-1, keepdim=True)
+    ds = bf16_round64(pr * (dp - delta) * live)
+    out.update(dq=bf16_round64(ds @ k.double() * scale), dk=bf16_round64(ds.transpose(-1, -2) @ q.double() * scale), dv=dv)
+    return out
+
+
+def row_err(got, ref):
+    """max over rows r of |got_r - ref_r| / max(|ref_r|, median_r |ref_r|) for 2-D [rows, n] tensors.  The median floor: some rows are zero or
+    nearly zero in the reference (dq of the first causal query rows) and their error scales with the other rows' size.  A zero median
+    (Sq = 1 under a causal cut: every dq row is zero) demands equality: 0.0 if equal, else inf."""
+    assert got.dim() == 2 and got.shape == ref.shape, (got.shape, ref.shape)
+    got, ref = got.detach().double(), ref.detach().double()
+    n = ref.norm(dim=1)
+    med = n.median()
+    if med.item() == 0.0:
+        return 0.0 if torch.equal(got, ref) else float('inf')
+    return ((got - ref).norm(dim=1) / torch.maximum(n, med)).max().item()
+
+
+def lse_err(lse, lse_ref, live_rows=None):
+    """max |lse - lse_ref| over the rows with at least one live key (bool mask of the shape of lse; None = all rows)"""
+    d = (lse.detach().double() - lse_ref.detach().double()).abs()
+    if live_rows is not None:
+        d = d[live_rows.to(d.device)]
+    return d.max().item()
+
+
+def lse_floor32(q, k, scale, live):
+    """lse_err of torch.logsumexp in float32 on the same masked scores: the float32 floor the lse bound is a multiple of"""
+    s = _attn_scores(q, k, scale, live)
+    rows = live.any(-1)
+    return lse_err(torch.logsumexp(s.float(), dim=-1), torch.logsumexp(s, dim=-1), rows)
